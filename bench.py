@@ -16,11 +16,19 @@ bench.py --gpus N, which spawns the N replica processes itself (spawn_replicas).
 The C4 leg (`c4_13b`) runs LLaMA-13B gptq.int4 batch 1 on every replica (BASELINE configs[4]).
 The timed K steps are centred on position 80 where the cache allows (SURVEY §8d workload).
 
-Also reported, on the same JSON line:
+A plain run (bench.py --gpus 1 --steps K --warmup W) builds the model, warms up, times the K
+steps and prints the headline line (metric, value, unit, ms_per_step, the step roofline against
+the HBM spec, memory). --dump-outputs DIR also writes what the timed decode path returned after
+its last timed step (DIR/tokens.npy: the ids of every row so far, prompt included; DIR/logits.npy:
+the last step's logits; float32), so that two builds can be compared output for output: the
+weights and prompts are seeded, hence identical from run to run.
+
+With --full, also reported on the same JSON line (each takes GPU or CPU runs of its own):
   roofline      dominant kernel (rms_2 + c_fc1/c_fc2 int4 GEMV + silu*mul, 1 launch per
                 layer, 45.2 MB of algorithmic bytes at 7B) timed with HIP events on the
-                stream it runs on, vs the 8 TB/s HBM peak;
-  step_roofline algorithmic bytes of a whole decode step / step time;
+                stream it runs on, vs the 8 TB/s HBM peak and the read rate achievable in this run
+                (which step_roofline, the algorithmic bytes of a whole decode step / step time
+                that every run reports, then also carries as frac_of_achievable);
   cpu_baseline  the numpy port of the reference's CPU path (oracle/, dequantize-every-call
                 like ColBlockQuantizedLinear's fallback, quantization.py:420-421) timed on a
                 bounded sample (one decode token through a few layers, scaled to 32);
@@ -242,9 +250,14 @@ def time_decode(model, B, prompt_len, S, warmup, steps, ws, seed=1234, use_graph
     from lit_llama.engine import DecodeSession
 
     cfg = model.config
+    assert steps >= 1, "--steps must be at least 1"
     skip = untimed_steps(prompt_len, S, warmup, steps)
-    total = prompt_len + 1 + skip + steps
-    assert total <= cfg.block_size, "positions beyond block_size"
+    # one session holds positions up to block_size: more timed steps than fit there run as further
+    # sessions of the same prompts, whose prefill and untimed steps stay outside the timing
+    seg_cap = cfg.block_size - (prompt_len + 1 + skip)
+    assert seg_cap >= 1, "positions beyond block_size"
+    segs = [min(seg_cap, steps - i) for i in range(0, steps, seg_cap)]
+    total = prompt_len + 1 + skip + segs[0]
     g = torch.Generator().manual_seed(seed)
     prompts = torch.randint(3, cfg.vocab_size, (B, prompt_len), generator=g).cuda()
     sess = DecodeSession(model, B, S, total, use_graph=use_graph)
@@ -254,25 +267,45 @@ def time_decode(model, B, prompt_len, S, warmup, steps, ws, seed=1234, use_graph
     sess.prefill(prompts)
     torch.cuda.synchronize()
     t_prefill = time.perf_counter() - t0
-    sess.capture()
-    if skip:
-        sess.decode(skip)
-    barrier(ws)
+    seconds = gpu_s = wall = pos_sum = kv_pos_sum = 0.0
+    for i, n in enumerate(segs):
+        if i:
+            sess.prefill(prompts)
+        sess.capture()
+        if skip:
+            sess.decode(skip)
+        barrier(ws)
+        torch.cuda.synchronize()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        ev0.record()
+        sess.decode(n)
+        ev1.record()
+        torch.cuda.synchronize()
+        seg_wall = time.perf_counter() - t0
+        barrier(ws)
+        seg_gpu = ev0.elapsed_time(ev1) / 1e3
+        seconds += max(seg_wall, seg_gpu)
+        gpu_s += seg_gpu
+        wall += seg_wall
+        # the step that reads position p writes slot p and attends p + 1 keys; the first timed
+        # step of a session runs at position prompt_len + skip
+        pos_sum += n * (prompt_len + skip + (n - 1) / 2.0)
+        # past the S-slot cache a step attends S keys: the position that step_bytes' KV term takes
+        kv_pos_sum += float(np.minimum(np.arange(n) + prompt_len + skip, S - 1).sum())
+    return dict(seconds=seconds, gpu_seconds=gpu_s, wall_seconds=wall, t_prefill=t_prefill,
+                pos_mean=pos_sum / steps, kv_pos_mean=kv_pos_sum / steps, tokens=B * steps, session=sess)
+
+
+def dump_outputs(sess, out_dir) -> None:
+    """--dump-outputs: what a caller of the timed decode path holds after its last timed step, as
+    float32 .npy files: tokens (B, T) the ids of every row so far (prompt, then one id per decode
+    step; exact in float32) and logits (B, padded_vocab_size) of the last step."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
     torch.cuda.synchronize()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    ev0.record()
-    sess.decode(steps)
-    ev1.record()
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t0
-    barrier(ws)
-    gpu_s = ev0.elapsed_time(ev1) / 1e3
-    # the step that reads position p writes slot p and attends p + 1 keys; the first timed
-    # step runs at position prompt_len + skip
-    pos_mean = prompt_len + skip + (steps - 1) / 2.0
-    return dict(seconds=max(wall, gpu_s), gpu_seconds=gpu_s, wall_seconds=wall, t_prefill=t_prefill,
-                pos_mean=pos_mean, tokens=B * steps, session=sess)
+    np.save(out / "tokens.npy", sess.output().cpu().numpy().astype(np.float32))
+    np.save(out / "logits.npy", sess.logits.float().cpu().numpy().astype(np.float32))
 
 
 def time_stub(steps, warmup, ws, step_s=1e-3):
@@ -472,7 +505,7 @@ def c4_leg(args, ws):
     m13 = build_model("13B", "gptq.int4")
     r = time_decode(m13, 1, args.prompt_len, args.max_seq_length, args.warmup, args.steps, ws)
     t, tok = aggregate(r["seconds"], r["tokens"], ws)
-    sb = step_bytes(m13, 1, r["pos_mean"])
+    sb = step_bytes(m13, 1, r["kv_pos_mean"])
     out = {"workload": "LLaMA-13B --quantize gptq.int4 greedy decode, batch 1 per replica",
            "value": round(tok / t, 2), "unit": "tokens/s", "n_replicas": ws,
            "ms_per_step": round(t / args.steps * 1e3, 4),
@@ -492,7 +525,7 @@ def config_leg(args, ws, name: str, mode, B: int, outliers=None, workload: str =
     m = build_model(name, mode, outliers=outliers)
     r = time_decode(m, B, args.prompt_len, args.max_seq_length, args.warmup, args.steps, ws)
     t, tok = aggregate(r["seconds"], r["tokens"], ws)
-    sb = step_bytes(m, B, r["pos_mean"])
+    sb = step_bytes(m, B, r["kv_pos_mean"])
     out = {"workload": workload, "value": round(tok / t, 2), "unit": "tokens/s", "n_replicas": ws, "batch": B,
            "ms_per_step": round(t / args.steps * 1e3, 4),
            "step_roofline_frac": round(sb / (r["seconds"] / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
@@ -512,10 +545,16 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--prompt-len", type=int, default=16)
     ap.add_argument("--max-seq-length", type=int, default=144)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bs8", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the LLaMA-13B replica leg (C4)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C1 (7B bf16 bs=1) and C3 (7B llm.int8 bs=8) legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the dominant-kernel roofline and the "
+                         "achievable read rate, batch 8, the CPU baseline and the C4 / C1 / C3 configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed path's outputs of its last step "
+                         "(DIR/tokens.npy, DIR/logits.npy, float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-bs8", action="store_true", help="with --full: skip the batch-8 leg")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the LLaMA-13B replica leg (C4)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C1 (7B bf16 bs=1) and C3 (7B llm.int8 bs=8) legs")
     ap.add_argument("--only-dominant", action="store_true",
                     help="profiling aid: only the dominant-kernel loop (for the PMC traffic passes)")
     ap.add_argument("--decode-only", action="store_true",
@@ -563,6 +602,8 @@ def main():
         return
     r = time_decode(model, args.batch, args.prompt_len, S, args.warmup, args.steps, ws, use_graph=not args.eager)
     t_max, tokens = aggregate(r["seconds"], r["tokens"], ws)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r["session"], args.dump_outputs)
     if args.decode_only:
         if rank == 0:
             print(json.dumps({"decode_only": True, "tokens_per_s": round(tokens / t_max, 2),
@@ -570,34 +611,51 @@ def main():
         return
     value = tokens / t_max
     ms_per_step = t_max / args.steps * 1e3
-    sb = step_bytes(model, args.batch, r["pos_mean"])
+    sb = step_bytes(model, args.batch, r["kv_pos_mean"])
     step_gbs = sb / (r["seconds"] / args.steps) / 1e9
     mem = {"max_reserved_gb": round(torch.cuda.max_memory_reserved() / 1e9, 3),
            "max_allocated_gb": round(torch.cuda.max_memory_allocated() / 1e9, 3),
            "reference_gb": "~5 (README.md:108, 7B gptq.int4)"}
 
-    k_s, k_bytes = time_dominant_kernel(model, args.batch)
-    k_gbs = k_bytes / k_s / 1e9
-    in_graph = graph_kernel_us()
-    ach = achievable_read_gbs()
+    # everything below the headline takes runs of its own: only with --full
+    roofline = ach = None
+    if args.full:
+        k_s, k_bytes = time_dominant_kernel(model, args.batch)
+        k_gbs = k_bytes / k_s / 1e9
+        in_graph = graph_kernel_us()
+        ach = achievable_read_gbs()
+        pmc = pmc_traffic()
+        head7 = args.batch == 1 and mode == "gptq.int4" and args.model == "7B"
+        roofline = {"bound": "hbm", "achieved": round(k_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(k_gbs / HBM_PEAK_GBS, 4),
+                    "achievable": round(ach, 1), "frac_of_achievable": round(k_gbs / ach, 4),
+                    "achievable_source": "llj_stream_read over 4 GB (measured in this run)",
+                    "traffic": round(pmc[0]) if pmc and head7 else None,
+                    "traffic_source": (f"profiles/{pmc[1]} (PMC FETCH_SIZE/WRITE_SIZE passes, "
+                                       f"profiled {pmc[2]:.2f} us)" if pmc and head7 else None),
+                    "kernel": "gemv_kernel<W4,NORM,SWIGLU> (rms_2 + c_fc1/c_fc2 + silu*mul)",
+                    "bytes_per_launch": k_bytes, "avg_launch_us": round(k_s * 1e6, 2),
+                    **({"in_graph_avg_launch_us": round(in_graph[0], 2),
+                        "in_graph_frac": round(k_bytes / (in_graph[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                        "in_graph_source": f"profiles/{in_graph[1]} (rocprofv3 kernel trace of bench.py --decode-only)"}
+                       if in_graph and head7 else {})}
 
-    pmc = pmc_traffic()
     bs8 = None
-    if not args.no_bs8 and args.batch != 8:
+    if args.full and not args.no_bs8 and args.batch != 8:
         del r["session"]
         r8 = time_decode(model, 8, args.prompt_len, S, args.warmup, args.steps, ws)
         t8, tok8 = aggregate(r8["seconds"], r8["tokens"], ws)
-        sb8 = step_bytes(model, 8, r8["pos_mean"])
+        sb8 = step_bytes(model, 8, r8["kv_pos_mean"])
         bs8 = {"value": tok8 / t8, "unit": "tokens/s", "ms_per_step": t8 / args.steps * 1e3,
                "step_roofline_frac": sb8 / (r8["seconds"] / args.steps) / 1e9 / HBM_PEAK_GBS}
         del r8["session"]
 
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and mode == "gptq.int4":
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline and mode == "gptq.int4":
         cpu = cpu_baseline(model)
 
     c4 = c1 = c3 = None
-    legs = args.model == "7B" and mode == "gptq.int4"
+    legs = args.full and args.model == "7B" and mode == "gptq.int4"
     r.pop("session", None)  # the headline's numbers stay in r; its graph and cache are freed
     if legs:
         del model
@@ -618,7 +676,6 @@ def main():
 
     if rank == 0:
         name = {"gptq.int4": "gptq.int4", "llm.int8": "llm.int8", "none": "bf16"}[args.quantize]
-        head7 = args.batch == 1 and mode == "gptq.int4" and args.model == "7B"
         line = {
             "metric": f"decode tokens/sec LLaMA-{args.model} {name} bs={args.batch}, 1xMI355X per replica",
             "value": round(value, 2),
@@ -639,22 +696,11 @@ def main():
                        "batch_per_gpu": args.batch, "prompt_len": args.prompt_len, "max_seq_length": S,
                        "timed_positions_mean": r["pos_mean"],
                        "parallelism": f"replicas x{ws} (no collective on the data path)"},
-            "roofline": {"bound": "hbm", "achieved": round(k_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(k_gbs / HBM_PEAK_GBS, 4),
-                         "achievable": round(ach, 1), "frac_of_achievable": round(k_gbs / ach, 4),
-                         "achievable_source": "llj_stream_read over 4 GB (measured in this run)",
-                         "traffic": round(pmc[0]) if pmc and head7 else None,
-                         "traffic_source": (f"profiles/{pmc[1]} (PMC FETCH_SIZE/WRITE_SIZE passes, "
-                                            f"profiled {pmc[2]:.2f} us)" if pmc and head7 else None),
-                         "kernel": "gemv_kernel<W4,NORM,SWIGLU> (rms_2 + c_fc1/c_fc2 + silu*mul)",
-                         "bytes_per_launch": k_bytes, "avg_launch_us": round(k_s * 1e6, 2),
-                         **({"in_graph_avg_launch_us": round(in_graph[0], 2),
-                             "in_graph_frac": round(k_bytes / (in_graph[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                             "in_graph_source": f"profiles/{in_graph[1]} (rocprofv3 kernel trace of bench.py --decode-only)"}
-                            if in_graph and head7 else {})},
+            "full": args.full,
+            **({"roofline": roofline} if roofline else {}),
             "decode_path": "launch chain (5 fused launches per layer)",
             "step_roofline": {"bytes_per_step": sb, "achieved": round(step_gbs, 1), "frac": round(step_gbs / HBM_PEAK_GBS, 4),
-                              "frac_of_achievable": round(step_gbs / ach, 4)},
+                              **({"frac_of_achievable": round(step_gbs / ach, 4)} if ach else {})},
             "reference_formula_tokens_per_s": round(r["tokens"] / (r["seconds"] + r["t_prefill"]), 2),
             "memory": mem,
             "cpu_baseline": cpu,

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 D=/tmp/$OUT
 mkdir -p $D $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-SHORT="--quantize llm.int8 --batch 1 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
+SHORT="--full --quantize llm.int8 --batch 1 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
 run() {  # tag counters
   timeout -s KILL 150 rocprofv3 --pmc $2 --output-format csv -d $D -o $1 -- python3 $R/bench.py $SHORT > $D/$1.log 2>&1
   echo "$1 rc=$?"

@@ -13,10 +13,10 @@ R=$GRAFT_REPO_ROOT
 D=$R/gpurun_out/$OUT
 mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
-SHORT="--steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
+SHORT="--full --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
 SQ="SQ_WAVE_CYCLES,SQ_BUSY_CYCLES,SQ_VALU_MFMA_BUSY_CYCLES,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_ACTIVE_INST_ANY,SQ_INSTS_VALU_MFMA_MOPS_BF16,SQ_INSTS_VALU_MFMA_MOPS_I8,GRBM_GUI_ACTIVE"
 if [ -z "$SKIP_TRACE" ]; then
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o trace -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-c4 > $D/bench_trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o trace -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-c4 > $D/bench_trace.log 2>&1
 echo trace done
 fi
 timeout -s KILL 170 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D -o bs1_fetch -- python3 $R/bench.py $SHORT > $D/bs1_fetch.log 2>&1

@@ -23,8 +23,8 @@ run() {  # tag counters bench-args...
   local rc=$?; echo "$tag rc=$rc"
   case $rc in 0) ;; *) cp $D/$tag.log $R/gpurun_out/ 2>/dev/null; exit $rc;; esac
 }
-B8="--batch 8 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
-C3="--quantize llm.int8 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
+B8="--full --batch 8 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
+C3="--full --quantize llm.int8 --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
 run bs8_fetch FETCH_SIZE $B8
 run bs8_write WRITE_SIZE $B8
 run bs8_sqa "SQ_WAVE_CYCLES,SQ_BUSY_CYCLES,SQ_VALU_MFMA_BUSY_CYCLES,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_ACTIVE_INST_ANY,GRBM_GUI_ACTIVE" $B8

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 D=/tmp/$OUT
 mkdir -p $D $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-SHORT="--steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
+SHORT="--full --steps 4 --warmup 1 --no-bs8 --no-c4 --no-cpu-baseline --eager"
 run() {  # tag counters extra-args
   timeout -s KILL 120 rocprofv3 --pmc $2 --output-format csv -d $D -o $1 -- python3 $R/bench.py $SHORT $3 > $D/$1.log 2>&1
   echo "$1 rc=$?"
