@@ -392,6 +392,27 @@ int llj_i8_norm_rowstats(const void* x, const void* norm_w, float eps, void* xn,
 int llj_i8_linear_resid(const void* A, int lda, const void* CB, const void* SCB, void* x, int ldx, int M, int N, int K,
                         const void* stats, void* stream);
 
+/* ---------------------------------------------------------------- LLaMA-Adapter (inference)
+ * The prefix cross-attention of an adapted layer (reference lit_llama/adapter.py:149-165):
+ *   y[m, h, :] += gating_factor[h] * softmax_j(q[m, h] . ak[h, j] / sqrt(hs)) . av[h, j, :]
+ * over the aT learned prefix keys / values ak, av (n_head, aT, head_size) = the K / V thirds of
+ * c_attn(adapter_wte.weight) (adapter.py:153-157; no RoPE, no mask, shared by all batch rows), a
+ * softmax of its own beside the causal one. gate: gating_factor as n_head fp32 values.
+ * 1 <= aT <= 64 (LLJ_EINVAL otherwise, nothing launched). */
+/* llj_attention (decode, one block per (head, row); adapter.py:145) with the prefix term in the same
+ * launch: y = bf16(O / L + gate[h] * Oa / La), one rounding. bf16, head_size 64 or 128; ak / av
+ * contiguous and 16-byte aligned. gate all zero: bitwise llj_attention. */
+int llj_attention_adapter(const void* q, const void* kcache, const void* vcache, void* y, const int* pos, int B, int T,
+                          int n_head, int head_size, int S, const void* ak, const void* av, const float* gate, int aT,
+                          void* stream);
+/* The prefix term added in place to M contiguous rows y (M, n_head * head_size) that another
+ * attention kernel wrote (llj_attention_prefill, llj_attention_split, llj_g_attention), adapter.py:164-165
+ * with the reference's rounding points for bf16 tensors: bf16(bf16(y) + bf16(gate * bf16(ay))). Any
+ * head_size with (aT * (head_size + 1) + 1024 + 4 * head_size) * 4 bytes of LDS <= 64 KiB; dt as the
+ * any-shape kernels (0 bf16, 1 fp32) for q, ak, av and y. */
+int llj_adapter_prefix_add(const void* q, const void* ak, const void* av, const float* gate, void* y, int M, int n_head,
+                           int head_size, int aT, int dt, void* stream);
+
 /* Measurement aid (no reference counterpart): reads `bytes` (a multiple of 16) at p once with
  * non-temporal 16-byte loads over `grid` workgroups of 256 and writes one float per workgroup to
  * out (grid floats). bench.py times it over a buffer far larger than the 256 MB MALL to report the

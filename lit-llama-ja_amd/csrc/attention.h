@@ -12,12 +12,27 @@
 #include "common.h"
 #include "i8ws.h"
 
+// 512 x 4 (128 keys per pass, half the serial score / softmax chain per lane of 256 x 8): 7B
+// gptq.int4 decode-only at position ~80, bs=1 847.4 -> 857.8 tok/s, bs=8 4321 -> 4355
+// (profiles/r04_attention_block_ab.json; 512 x 8 and 1024 x 2 in between)
+#ifndef LLJ_ATT_NTH
+#define LLJ_ATT_NTH 512  // threads per (row, head) block
+#endif
+#ifndef LLJ_ATT_SPEC_BATCH
+#define LLJ_ATT_SPEC_BATCH 0  // half speculative pass at any grid size (A/B: option LLJ_OPT_ATT_SPEC_BATCH)
+#endif
+#ifndef LLJ_ATT_U
+#define LLJ_ATT_U 4  // keys per 16-lane group per pass
+#endif
+
 namespace llj {
 
-template <int HS, int NTH>
+constexpr int kAdpMaxT = 64;  // longest adapter prefix (ADP below; adapter.hip)
+
+template <int HS, int NTH, bool ADP = false>
 constexpr int attention_lds_floats() {
   constexpr int NWV = NTH / 64;  // waves: one (max, sum, HS outputs) partial each
-  return 2 * NWV + NWV * HS;
+  return 2 * NWV + NWV * HS + (ADP ? kAdpMaxT : 0);  // ADP: the prefix scores
 }
 
 // LLM.int8() statistics of attention output rows for the int8 c_proj (i8ws.h): the calling wave
@@ -61,7 +76,17 @@ __device__ __forceinline__ void softmax_merge(float& mx, float& l, float* o, con
 template <int HS>
 constexpr int kAttPart = HS + 4;  // floats per partial record: HS outputs, max, sum, 2 pad (16-byte records)
 
-template <int HS, int U, int NTH, bool PART = false, int SPECU = U / 2, bool ILV = false>
+// ADP (llj_attention_adapter; never with PART): the LLaMA-Adapter prefix term of reference
+// adapter.py:149-165 in the same launch -- aT <= kAdpMaxT learned keys / values per head (ak, av:
+// (nh, aT, HS) bf16, no RoPE, no mask, shared by all rows) under a softmax of their own, added as
+// y = bf16(O / L + gate[h] * Oa / La). Key group kg scores prefix keys kg, kg + NG, ... from rows
+// loaded with the speculative pass (nothing of it depends on the position) and leaves the scores
+// in aT LDS floats ahead of the barrier that exists anyway; the output tail forms the prefix
+// softmax and sum_j p_j av[h, j, d] beside O / L, with the first kAdpPre value rows prefetched into
+// registers before the key loop and longer prefixes read from L2 (<= 16 KB per head, the same for
+// every row): no second barrier, no second merge tree.
+constexpr int kAdpPre = 16;
+template <int HS, int U, int NTH, bool PART = false, int SPECU = U / 2, bool ILV = false, bool ADP = false>
 __device__ __forceinline__ void attention_body(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                                const bf16_t* __restrict__ vc, bf16_t* __restrict__ y,
                                                const int* __restrict__ pos, int T, int S, int nh, float scale_log2,
@@ -69,13 +94,17 @@ __device__ __forceinline__ void attention_body(const bf16_t* __restrict__ q, con
                                                int split = 0, float* __restrict__ part = nullptr,
                                                uint32_t* __restrict__ st = nullptr, float thr = 0.f,
                                                uint32_t* __restrict__ clr = nullptr, int clr_words = 0,
-                                               bool spec_ok = false) {
+                                               bool spec_ok = false, const bf16_t* __restrict__ ak = nullptr,
+                                               const bf16_t* __restrict__ av = nullptr,
+                                               const float* __restrict__ gate = nullptr, int aT = 0) {
+  static_assert(!(ADP && PART), "the prefix term needs the normalized output");
   constexpr int DPL = HS / 16;
   constexpr int NG = NTH / 16;
   constexpr int NWV = NTH / 64;
   float* s_m = lds;                     // [NWV]
   float* s_l = s_m + NWV;               // [NWV]
   float* s_o = s_l + NWV;               // [NWV][HS]
+  float* s_a = s_o + NWV * HS;          // [kAdpMaxT] prefix scores (ADP)
   LLJ_STAMP(0);
   if (clr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)  // a statistics block to zero (int8 decode)
     for (int i = threadIdx.x; i < clr_words; i += NTH) clr[i] = 0u;
@@ -117,6 +146,32 @@ __device__ __forceinline__ void attention_body(const bf16_t* __restrict__ q, con
   // past p than the latency saved (7B bs=8: 1.79 -> 1.87 ms)
   const bool spec = (!PART || ILV) && spec_ok;
   if (spec) load_pass((ILV ? split * NG : 0) + kg, S, kw, vw, 0, SPECU);
+  // ADP: this group's prefix key rows and, in the threads of the output tail, the first value rows
+  constexpr int AKG = (kAdpMaxT + NG - 1) / NG;
+  uint32_t akw[ADP ? AKG : 1][DPL / 2];
+  uint32_t avp[ADP ? kAdpPre : 1];  // bf16 bits, one VGPR each; first touched in the tail
+  float ag = 0.f;
+  if constexpr (ADP) {
+    const bf16_t* akh = ak + (size_t)h * aT * HS;
+#pragma unroll
+    for (int a = 0; a < AKG; ++a) {
+      const int j = kg + NG * a < aT ? kg + NG * a : 0;
+      const bf16_t* src = akh + (size_t)j * HS + sub * DPL;
+      if constexpr (DPL == 8) {
+        const uint4 w = *reinterpret_cast<const uint4*>(src);
+        akw[a][0] = w.x; akw[a][1] = w.y; akw[a][2] = w.z; akw[a][3] = w.w;
+      } else {
+        const uint2 w = *reinterpret_cast<const uint2*>(src);
+        akw[a][0] = w.x; akw[a][1] = w.y;
+      }
+    }
+    if (threadIdx.x < HS) {
+      const bf16_t* avh = av + (size_t)h * aT * HS + threadIdx.x;
+#pragma unroll
+      for (int i = 0; i < kAdpPre; ++i) avp[i] = avh[(size_t)(i < aT ? i : 0) * HS];
+    }
+    ag = gate[h];
+  }
   const int ps = pos[t];
   const int nvalid = ps < S ? ps + 1 : S;
   // key range of this block (the whole valid range unless split)
@@ -176,6 +231,16 @@ __device__ __forceinline__ void attention_body(const bf16_t* __restrict__ q, con
       mx = mn;
     }
   }
+  if constexpr (ADP) {  // prefix scores (log2 domain, as s above): one LDS float per prefix key
+#pragma unroll
+    for (int a = 0; a < AKG; ++a) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < DPL / 2; ++i) s += qf[2 * i] * bflo(akw[a][i]) + qf[2 * i + 1] * bfhi(akw[a][i]);
+      s = row16_sum(s);
+      if (sub == 0 && kg + NG * a < aT) s_a[kg + NG * a] = s;
+    }
+  }
   LLJ_STAMP(3);
   // combine the key groups: the four 16-lane groups of a wave with lane swaps (rows 0+1 and
   // 2+3, then the two halves; every lane of a group holds the group's max and sum and its
@@ -226,7 +291,54 @@ __device__ __forceinline__ void attention_body(const bf16_t* __restrict__ q, con
       LLJ_STAMP(5);
       return;
     }
-    const uint32_t ob = (uint32_t)f2bf(O / L);
+    float r = O / L;
+    if constexpr (ADP) {  // + gate * softmax(prefix scores) . av[h, :, d]; La >= 1 (the maximum's own term)
+      // the softmax once per 16-lane row instead of once per lane: lane i of a row takes the scores
+      // i, i + 16, ... (one batch of LDS reads; slots past aT hold no score and are masked), the
+      // row's DPP max / sum give Ma / La, and the probabilities come back as wave-uniform values
+      // (readlane of row 0: every row holds the same ones)
+      static_assert(kAdpPre == 16, "one prefetched value row per lane of a DPP row");
+      constexpr int AKR = kAdpMaxT / 16;
+      const int li = threadIdx.x & 15;
+      float pk[AKR];
+      float Ma = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < AKR; ++k) {
+        pk[k] = s_a[li + 16 * k];
+        Ma = fmaxf(Ma, li + 16 * k < aT ? pk[k] : -INFINITY);
+      }
+      Ma = row16_max(Ma);
+      float La = 0.f;
+#pragma unroll
+      for (int k = 0; k < AKR; ++k) {
+        pk[k] = (16 * k < aT && li + 16 * k < aT) ? exp2f(pk[k] - Ma) : 0.f;
+        La += pk[k];
+      }
+      La = row16_sum(La);
+      auto prob = [&](int k, int i) {  // p of prefix key 16 k + i
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pk[k]), i));
+      };
+      float Oa = 0.f;
+      // (an empty asm on each prefetched value: the compiler otherwise moves the bf16 -> fp32 shift up
+      // to the loads and waits for them there, ahead of the position read: + 0.3 us per launch)
+#pragma unroll
+      for (int i = 0; i < kAdpPre; ++i) asm volatile("" : "+v"(avp[i]));
+#pragma unroll
+      for (int i = 0; i < kAdpPre; ++i) Oa += prob(0, i) * bflo(avp[i]);  // rows past aT: p = 0
+      const bf16_t* avh = av + (size_t)h * aT * HS + d;
+#pragma unroll
+      for (int k = 1; k < AKR; ++k) {
+        if (16 * k < aT) {  // uniform: prefixes longer than the prefetched rows read the rest from L2
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int j = 16 * k + i < aT ? 16 * k + i : 0;  // (p = 0 past aT)
+            Oa += prob(k, i) * bf2f(avh[(size_t)j * HS]);
+          }
+        }
+      }
+      r += ag * (Oa / La);
+    }
+    const uint32_t ob = (uint32_t)f2bf(r);
     const uint32_t pr = lane_xor1(ob);
     if (!(d & 1)) {
       const size_t eo = (size_t)m * C + h * HS + d;

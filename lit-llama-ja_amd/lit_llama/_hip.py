@@ -82,6 +82,8 @@ SIGNATURES = {
     "llj_g_argmax": [_P, _I, _I, _I, _P, _P, _I, _P, _P],
     "llj_g_sample": [_P, _I, _I, _I, _F, _I, _P, ctypes.c_ulonglong, _P, _P, _I, _P, _P],
     "llj_g_i8_linear": [_P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _I, _P],
+    "llj_attention_adapter": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
+    "llj_adapter_prefix_add": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 _lib = None

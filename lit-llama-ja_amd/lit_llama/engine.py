@@ -19,7 +19,7 @@ from __future__ import annotations
 import torch
 
 from . import _hip
-from .model import LLaMA, _Work, _enable_i8_handoff
+from .model import LLaMA, _Work
 
 
 class DecodeSession:
@@ -99,7 +99,7 @@ class DecodeSession:
         else:
             need_i8 = any(s[0] == 2 for layer in self.specs["layers"] for s in layer) or self.specs["head"][0] == 2
             self.work = _Work(m.config, B, self.dev, need_i8, self.S)
-            _enable_i8_handoff(self.work, self.specs)
+            m._enable_i8_handoff(self.work, self.specs)
         self.graph = None  # the caches / operands may have changed
 
     def _reset_handoff(self):

@@ -411,7 +411,7 @@ class LLaMA(nn.Module):
             need_i8 = any(s[0] == 2 for layer in specs["layers"] for s in layer) or specs["head"][0] == 2
             w = _Work(cfg, M, dev, need_i8, S, gemm=self._gemm_ok(specs, M))
             w.flash = self._flash_ok(pos, T, S)
-            _enable_i8_handoff(w, specs)
+            self._enable_i8_handoff(w, specs)
         st = _hip.stream()
         ids = idx.reshape(-1).to(torch.int32)
         if w.generic:
@@ -485,6 +485,26 @@ class LLaMA(nn.Module):
             out.append(t)
         return ao, out, kpad
 
+    def _enable_i8_handoff(self, w, specs) -> None:
+        """The LLM.int8 decode statistics hand-off for this model's scratch (a subclass may decline)."""
+        _enable_i8_handoff(w, specs)
+
+    def _adapter(self, i):
+        """(ak, av, gate, aT) of layer i's learned attention prefix, or None: this model has none
+        (lit_llama.adapter.LLaMA overrides)."""
+        return None
+
+    def _adapter_fused(self) -> bool:
+        """prefix term inside the one-block decode attention launch (llj_attention_adapter)"""
+        return True
+
+    def _prefix_add(self, ad, w, M, st):
+        """w.y += gate * softmax(q . AK^T / sqrt(hs)) . AV on rows another attention kernel wrote."""
+        ak, av, gate, aT = ad
+        cfg = self.config
+        _hip.call("llj_adapter_prefix_add", w.q.data_ptr(), ak.data_ptr(), av.data_ptr(), gate.data_ptr(),
+                  w.y.data_ptr(), M, cfg.n_head, cfg.n_embd // cfg.n_head, aT, w.dt, st)
+
     def _flash_ok(self, pos, T, S):
         """prompt rows attend through the flash kernel: T >= FLASH_MIN_T, head_size 64 / 128,
         positions contiguous and inside the cache without wrapping (one host read of pos; prompts
@@ -495,9 +515,18 @@ class LLaMA(nn.Module):
         p = pos.cpu()
         return bool((p[1:] - p[:-1] == 1).all()) and int(p[0]) + T <= S
 
-    def _attention(self, w, kc, vc, pos, B, T, S, st):
+    def _attention(self, w, kc, vc, pos, B, T, S, st, i=None):
+        """Attention of layer i into w.y; with an adapter prefix (_adapter(i)) the one-block decode
+        kernel takes the prefix term in its own launch, the other kernels are followed by
+        llj_adapter_prefix_add."""
         cfg = self.config
         C, nh = cfg.n_embd, cfg.n_head
+        ad = None if i is None else self._adapter(i)
+        if ad is not None and not w.flash and w.att_ws is None and self._adapter_fused():
+            ak, av, gate, aT = ad
+            _hip.call("llj_attention_adapter", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
+                      pos.data_ptr(), B, T, nh, C // nh, S, ak.data_ptr(), av.data_ptr(), gate.data_ptr(), aT, st)
+            return
         if w.flash:
             _hip.call("llj_attention_prefill", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
                       pos.data_ptr(), B, T, nh, C // nh, S, st)
@@ -507,6 +536,8 @@ class LLaMA(nn.Module):
         else:
             _hip.call("llj_attention", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
                       pos.data_ptr(), B, T, nh, C // nh, S, st)
+        if ad is not None:
+            self._prefix_add(ad, w, B * T, st)
 
     def _gemm_ok(self, specs, M):
         cfg = self.config
@@ -538,7 +569,7 @@ class LLaMA(nn.Module):
                           w.xn.data_ptr(), None, M, C, st)
                 _hip.call("llj_gemm_qkv_rope", _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa), w.q.data_ptr(),
                           kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, st)
-            self._attention(w, kc, vc, pos, B, T, S, st)
+            self._attention(w, kc, vc, pos, B, T, S, st, i)
             self._gemm_resid(_gz(fp, blk.attn.c_proj), w.y, wp, sp, w.x, M, C, C, w, st)
             if f1 != f2:
                 raise TypeError("c_fc1 and c_fc2 must share a weight format")
@@ -621,6 +652,9 @@ class LLaMA(nn.Module):
                       self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, w.dt, st)
             _hip.call("llj_g_attention", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(), pos.data_ptr(),
                       B, T, C, nh, S, w.dt, st)
+            ad = self._adapter(i)
+            if ad is not None:
+                self._prefix_add(ad, w, M, st)
             self._glinear(sp, w.y, M, C, C, w.x, w.x, st)
             _hip.call("llj_g_rmsnorm", w.x.data_ptr(), C, blk.rms_2.scale.data_ptr(), blk.rms_2.eps, w.xn.data_ptr(), C,
                       M, C, w.dt, st)
@@ -676,13 +710,14 @@ class LLaMA(nn.Module):
                           w.h_st.numel(), Linear8bitLtThreshold, st)
                 _hip.call("llj_i8_linear_resid", w.y.data_ptr(), C, wp.data_ptr(), P(sp), w.x.data_ptr(), C, M, C, C,
                           w.y_st.data_ptr(), st)
-            elif w.att_merge and not w.flash and fp in (0, 1, 3):  # split partials, merged by c_proj (A/B)
+            elif w.att_merge and not w.flash and fp in (0, 1, 3) and self._adapter(i) is None:
+                # split partials, merged by c_proj (A/B); y is never materialized, so not with a prefix term
                 _hip.call("llj_attention_part", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), pos.data_ptr(), B, T, nh,
                           C // nh, S, w.att_merge, w.att_part.data_ptr(), st)
                 _hip.call("llj_linear_resid_attn", fp, w.att_part.data_ptr(), w.att_merge, nh, wp.data_ptr(), P(sp),
                           w.x.data_ptr(), C, C, C, P(w.nst) if w.hand else None, st)
             else:
-                self._attention(w, kc, vc, pos, B, T, S, st)
+                self._attention(w, kc, vc, pos, B, T, S, st, i)
                 self._resid(fp, w.y, wp, sp, w.x, M, C, C, w, st, w.nst if w.hand else None)
             # 4. rms_2 + fc1/fc2 + silu*mul
             if f1 != f2:
@@ -864,6 +899,9 @@ class _OneBlock:
 
     def _blocks_generic(self, *a):
         LLaMA._blocks_generic(self, *a)
+
+    def _adapter(self, i):
+        return None
 
     _glinear = staticmethod(LLaMA._glinear)
 
