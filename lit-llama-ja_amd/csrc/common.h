@@ -76,19 +76,10 @@ __device__ __forceinline__ i32x4 mfma_i8(i32x4 a, i32x4 b, i32x4 c) {
 }
 
 
-#ifndef LLJ_OUT_STORE
-#define LLJ_OUT_STORE 1  // 1 agent-scope relaxed atomic store (sc1, write-through; measured 7B: bs=1 1.167 -> 1.151 ms, bs=8 1.819 -> 1.789), 0 plain, 2 non-temporal
-#endif
-// 4-byte store of an epilogue output (a bf16 column pair) through a vector store
+// 4-byte store of an epilogue output (a bf16 column pair) through a vector store: an agent-scope relaxed
+// atomic store (sc1, write-through; measured against a plain store, 7B: bs=1 1.167 -> 1.151 ms, bs=8 1.819 -> 1.789)
 __device__ __forceinline__ void st_out32(void* dst, uint32_t v) {
-  uint32_t* p = reinterpret_cast<uint32_t*>(dst);
-#if LLJ_OUT_STORE == 1
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#elif LLJ_OUT_STORE == 2
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
+  __hip_atomic_store(reinterpret_cast<uint32_t*>(dst), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // host-side A/B options (options.hip, llj_set_option): -1 = the site's build default

@@ -40,6 +40,12 @@
 // Tile order is XCD-aware: the 8 XCDs take contiguous ranges of tiles; inside a range bf16 weights
 // go m fastest (the row tiles of one weight panel run together on one XCD and share it through its
 // L2), int4 weights n fastest (one 128-row A panel shared while the XCD sweeps the columns).
+//
+// Which kernel runs by default (gemm_run): below 256 rows every format takes gemm_kernel with 128-row
+// tiles; W8 and grouped int4 always do. From 256 rows on: bf16 -> gemm_glds_kernel (LDS-DMA, 256 x 256
+// or 256 x 128 by gemm_glds_run's tile-time estimate); int4 with integral zeros -> gemm_glds_kernel<GWF_W4Z>
+// (convert-once, 256 x 128); other int4 and LLM.int8 -> gemm_kernel with 256-row tiles. The runtime
+// options LLJ_OPT_GEMM_GLDS / LLJ_OPT_GEMM_W4Z move bf16 and int4 between those kernels.
 #include <cstdlib>
 
 #include "common.h"
@@ -95,15 +101,9 @@ struct GemmParams {
 // element is computed and stored (gemm_store_elem) -- one load latency per block instead of a
 // load -> store dependence per element (7B 2048-token window: the QKV and silu * mul GEMMs ran
 // 20-26 % slower than the plain store GEMM of the same shape with per-element loads).
-#ifndef LLJ_QKV_LDS
-#define LLJ_QKV_LDS 1  // LDS-DMA GEMM at 256 x 128 (bf16, convert-once int4): QKV epilogue through LDS, 16-byte row stores
-#endif
-#ifndef LLJ_GLDS_LDS_EPI
-#define LLJ_GLDS_LDS_EPI 1  // LDS-DMA GEMM at 256 x 128: store / residual / SwiGLU epilogues through LDS, 16-byte rows
-#endif
-#ifndef LLJ_QKV_GI
-#define LLJ_QKV_GI 4  // LDS-DMA GEMM QKV epilogue: 16-row blocks whose RoPE operands are loaded together (A/B)
-#endif
+// (The LDS-DMA GEMM at 256 x 128, bf16 and convert-once int4, instead sends its QKV / store / residual /
+// SwiGLU epilogues through LDS and stores 16-byte row segments.)
+constexpr int kQkvGI = 4;  // LDS-DMA GEMM QKV epilogue: 16-row blocks whose RoPE operands are loaded together
 #ifndef LLJ_QKV_ABL
 #define LLJ_QKV_ABL 0  // prompt QKV epilogue timing ablations (profiling only): 1 no RoPE operand loads, 2 no stores
 #endif
@@ -195,41 +195,15 @@ __device__ __forceinline__ void gemm_store_elem(const GemmParams& p, float y, in
 }
 
 constexpr int kGBM = 128, kGBN = 128, kGBK = 64, kGNT = 256;
-#ifndef LLJ_GEMM_PRIO
-#define LLJ_GEMM_PRIO 0
-#endif
-#ifndef LLJ_GEMM_MFAST
-#define LLJ_GEMM_MFAST 1
-#endif
-#ifndef LLJ_GDEPTH
-#define LLJ_GDEPTH 2  // W4: chunks in flight per thread (register ring); bf16 keeps 1 (registers)
-#endif
 // 256 x 128 tiles with 8 waves (4 row groups x 2 column groups of 64 x 64) for M >= 256: a weight
 // panel's 128-deep chunk feeds twice the rows (A + B bytes per MFMA 0.75x), one workgroup per CU
-#ifndef LLJ_GEMM_BM256
-#define LLJ_GEMM_BM256 1  // bf16 (7B 2048-token window 70.5 -> 42.6 ms with 2 chunks in flight)
-#endif
-#ifndef LLJ_GEMM_BM256_I8
-#define LLJ_GEMM_BM256_I8 1  // LLM.int8
-#endif
-#ifndef LLJ_GEMM_BM256_W4
-#define LLJ_GEMM_BM256_W4 1  // int4 W4P (39.6 -> 38.4 ms; 256 VGPRs + 64-72 B of scratch per lane)
-#endif
-#ifndef LLJ_GEMM_W4_WIDE
-#define LLJ_GEMM_W4_WIDE 0  // int4 256-row tiles as 2 x 4 waves of 128 x 32 (A/B)
-#endif
-#ifndef LLJ_GEMM_MFAST_W4
-#define LLJ_GEMM_MFAST_W4 0  // int4: m-fastest tile order too (A/B)
-#endif
-#ifndef LLJ_GDEPTH_W4_256
-#define LLJ_GDEPTH_W4_256 LLJ_GDEPTH  // int4 256-row tiles (188 VGPRs at 2 chunks in flight)
-#endif
-#ifndef LLJ_GDEPTH_DENSE
-#define LLJ_GDEPTH_DENSE 1  // bf16 / int8 in 128-row tiles (32 VGPRs of A + B per chunk in flight)
-#endif
-#ifndef LLJ_GDEPTH_DENSE256
-#define LLJ_GDEPTH_DENSE256 2  // bf16 / int8 in 256-row tiles (7B bf16 window 59.6 ms at 1, 42.6 at 2)
-#endif
+// (measured against 128-row tiles, 7B 2048-token window: bf16 70.5 -> 42.6 ms with 2 chunks in flight;
+// int4 W4P 39.6 -> 38.4 ms at 256 VGPRs + 64-72 B of scratch per lane)
+// chunks in flight per thread (register ring):
+constexpr int kGDepth = 2;                // nibble-coded and grouped int4 in 128-row tiles
+constexpr int kGDepthW4_256 = kGDepth;    // int4 256-row tiles (188 VGPRs at 2 chunks in flight)
+constexpr int kGDepthDense = 1;           // bf16 / int8 in 128-row tiles (32 VGPRs of A + B per chunk in flight)
+constexpr int kGDepthDense256 = 2;        // bf16 / int8 in 256-row tiles (7B bf16 window 59.6 ms at 1, 42.6 at 2)
 constexpr int kAP = kGBK + 8;  // A / bf16-B LDS row pitch (elements): 144 B
 
 template <int WF>
@@ -260,11 +234,8 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   constexpr bool GRP = WF == GWF_W4G;                  // grouped int4: dequantized to the weight values
   constexpr bool I8 = WF == GWF_I8;                    // LLM.int8(): int8 MFMA + fp16 outlier side product
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // wave grid: WRN row groups x WCN column groups of (16 MI) x (16 NJ) outputs; int4 256-row tiles
-  // optionally 2 x 4 waves of 128 x 32 (LLJ_GEMM_W4_WIDE: each B fragment dequantized by 2 waves, not 4)
-  constexpr bool WIDE = WF == GWF_W4 && BM == 256 && LLJ_GEMM_W4_WIDE;
-  constexpr int WRN = WIDE ? 2 : BM / 64;  // row groups of waves
-  constexpr int WCN = 2 * BM / 64 / WRN;   // column groups (2 * BM threads = 2 * BM / 64 waves)
+  // wave grid: WRN row groups x WCN column groups of 64 x 64 = (16 MI) x (16 NJ) outputs
+  constexpr int WRN = BM / 64, WCN = 2;  // 2 * BM threads = 2 * BM / 64 waves
   constexpr int MI = BM / WRN / 16, NJ = kGBN / WCN / 16;
   const int wr = wave % WRN, wc = wave / WRN;
   const int row = lane & 15, g = lane >> 4;
@@ -273,11 +244,12 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   const int total = mtiles * ntiles;
   int t = blockIdx.x;
   if (total % 8 == 0) t = (t % 8) * (total / 8) + t / 8;  // contiguous tile range per XCD
-  // m fastest (LLJ_GEMM_MFAST): the workgroups resident on one XCD cover a few weight column
+  // m fastest: the workgroups resident on one XCD cover a few weight column
   // panels x every row panel, so a weight panel is fetched once and shared through L2 by all
   // its row tiles (n fastest re-streamed every weight panel once per 128-row panel)
-  // (bf16 weights: 7B T = 2048 window 86.3 -> 71.9 ms; int4 weights, 4x smaller: 40.0 vs 40.6 ms, kept n fastest)
-  constexpr bool MF = (WF == GWF_BF16 || I8 || (WF == GWF_W4 && LLJ_GEMM_MFAST_W4)) && LLJ_GEMM_MFAST;
+  // (measured against n fastest, 7B T = 2048 window: bf16 weights 86.3 -> 71.9 ms; int4 weights, 4x smaller:
+  // 40.0 vs 40.6 ms, kept n fastest)
+  constexpr bool MF = WF == GWF_BF16 || I8;
   const int nb = MF ? t / mtiles : t % ntiles, mb = MF ? t % mtiles : t / ntiles;
   const int m0 = mb * BM, n0 = nb * kGBN;
 
@@ -300,8 +272,8 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   // GWF_I8: the thread's half of its row of the quantized activation (128 B per 128-deep chunk)
   const int8_t* aqsrc = I8 ? L8.aq + (size_t)agm * K + ah * 64 : nullptr;
   // register ring of GDEPTH chunks in flight (chunk c lives in slot c % GDEPTH)
-  constexpr int GDEPTH = (WF == GWF_W4 && BM == 256) ? LLJ_GDEPTH_W4_256
-                         : (NIB || GRP) ? LLJ_GDEPTH : BM == 256 ? LLJ_GDEPTH_DENSE256 : LLJ_GDEPTH_DENSE;
+  constexpr int GDEPTH = (WF == GWF_W4 && BM == 256) ? kGDepthW4_256
+                         : (NIB || GRP) ? kGDepth : BM == 256 ? kGDepthDense256 : kGDepthDense;
   constexpr int BV = (WF == GWF_W4 || GRP) ? 1 : WF == GWF_W8 ? 2 : BM == 256 ? 2 : 4;  // GWF_I8: 4 (64 B of its tile block)
   // bf16 B with 256-row tiles: 512 threads over the 128 weight rows, a quarter row (32 B) each
   const int br = BM == 256 ? tid >> 2 : ar, bq = BM == 256 ? tid & 3 : ah;
@@ -458,7 +430,6 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
               bf16x8, *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(Bs(buf)) + n * kAP + 32 * s + 8 * g));
         }
       }
-      if (LLJ_GEMM_PRIO) __builtin_amdgcn_s_setprio(1);  // the MFMA cluster ahead of the other waves' staging
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -466,7 +437,6 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
           acc[i][j] = mfma_bf16(af[i], bfr[j], acc[i][j]);
           if constexpr (WF == GWF_W8) acc[i][j] = mfma_bf16(af[i], bhi[j], acc[i][j]);
         }
-      if (LLJ_GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
     }
   };
 #pragma unroll
@@ -690,64 +660,25 @@ static int gemm_launch(const GemmParams& p, hipStream_t s) {
 // hits 16 distinct bank slots. int4: the 128 + zero offset is removed with the row sums of A,
 // which the waves form from the A fragments they already hold (v_dot2 with (1, 1); wave column wc
 // sums the 16-row blocks i = wc mod WN) and combine through LDS after the loop.
-#ifndef LLJ_GEMM_GLDS_BF16
-#define LLJ_GEMM_GLDS_BF16 1  // 7B 2048-token bf16 window 43.1 -> 36.5 ms (profiles/r04_prefill_ab.json)
-#endif
-#ifndef LLJ_GEMM_GLDS_W4
-#define LLJ_GEMM_GLDS_W4 0  // int4: 42.5 ms vs 37.6 with the register-staged 256-row kernel
-#endif
-#ifndef LLJ_GLDS_W4_WN
-#define LLJ_GLDS_W4_WN 4
-#endif
-#ifndef LLJ_GLDS_PRE
-#define LLJ_GLDS_PRE 1  // 256 x 128 tiles: read both MFMA steps' fragments of a chunk before its MFMAs (bf16 window 35.9 -> 35.4 ms)
-#endif
-#ifndef LLJ_GLDS_GROUPM
-#define LLJ_GLDS_GROUPM 0  // A/B only: grouped tile order (row tiles per group); 0 = the m- / n-fastest orders below
-#endif
-#ifndef LLJ_GLDS_NFAST_W4Z
-#define LLJ_GLDS_NFAST_W4Z 1  // convert-once int4 LDS-DMA GEMM: n-fastest tile order (A/B)
-#endif
-#ifndef LLJ_GLDS_NFAST_BF16
-#define LLJ_GLDS_NFAST_BF16 0  // bf16 LDS-DMA GEMM: n-fastest tile order (A/B)
-#endif
-#ifndef LLJ_GLDS_FDB
-#define LLJ_GLDS_FDB 1  // LDS-DMA GEMM at 256 x 128: chunk t + 1's fragments read during chunk t's MFMAs (A/B)
-#endif
-#ifndef LLJ_FDB_DSPM
-#define LLJ_FDB_DSPM 0  // fragment double buffering: LDS fragment reads per MFMA in the sched_group pattern (0: the scheduler's)
-#endif
-#ifndef LLJ_W4Z_PRIO
-#define LLJ_W4Z_PRIO 0  // convert-once int4: s_setprio around the MFMA clusters (1; 0: none, so the conversion interleaves with them)
-#endif
-#ifndef LLJ_W4Z_WAVES
-#define LLJ_W4Z_WAVES 8  // convert-once int4: waves converting a chunk's codes (8 or 4)
-#endif
-#ifndef LLJ_W4Z_SPLIT
-#define LLJ_W4Z_SPLIT 1  // convert-once int4, 8 converting waves: codes read before the fragment reads (A/B)
-#endif
-#ifndef LLJ_W4Z_IGLP
-#define LLJ_W4Z_IGLP 1  // convert-once int4: sched_group_barrier interleave of the conversion with the MFMAs
-#endif
-#ifndef LLJ_W4Z_VPM
-#define LLJ_W4Z_VPM 1  // VALU instructions per MFMA in that interleave (with fragment double buffering: 1 vs 2 vs 3 = 29.4-29.5 vs 29.9-30.0 vs 31.1 ms per 7B window)
-#endif
-#ifndef LLJ_W4Z_AFTER
-#define LLJ_W4Z_AFTER 0  // convert-once int4: the converting waves convert after their MFMAs (A/B)
-#endif
-#ifndef LLJ_GLDS_COST128
-#define LLJ_GLDS_COST128 55  // time of a 256 x 128 tile in % of a 256 x 256 one (tile-shape choice)
-#endif
+// per-format defaults of the runtime option LLJ_OPT_GEMM_GLDS (glds_enabled)
+constexpr bool kGldsBf16 = true;  // measured against the register-staged 256-row kernel: 7B 2048-token bf16 window 43.1 -> 36.5 ms (profiles/r04_prefill_ab.json)
+constexpr bool kGldsW4 = false;   // per-fragment int4: 42.5 ms vs 37.6 with the register-staged 256-row kernel
+constexpr int kGldsW4WN = 4;      // per-fragment int4 at BN 128: waves along N
+// convert-once int4: VALU instructions per MFMA in the interleave of the conversion with the MFMAs
+// (with fragment double buffering: 1 vs 2 vs 3 = 29.4-29.5 vs 29.9-30.0 vs 31.1 ms per 7B window)
+constexpr int kW4zVPM = 1;
+// time of a 256 x 128 tile in % of a 256 x 256 one (tile-shape choice; the runtime option LLJ_OPT_GLDS_COST128's fallback)
+constexpr int kGldsCost128 = 55;
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 template <int WF, int BN>
 struct GldsGeo {
   // waves along N: 4 at BN 256; at BN 128, 2 for bf16 and the convert-once int4 (64 x 64 per wave:
-  // fewer A fragment reads) and LLJ_GLDS_W4_WN for the per-fragment int4 (4: 128 x 32 per wave, each B
+  // fewer A fragment reads) and kGldsW4WN for the per-fragment int4 (4: 128 x 32 per wave, each B
   // fragment dequantized by 2 waves instead of 4)
   static constexpr bool CVT = WF == GWF_W4Z;
-  static constexpr int WN = BN == 256 ? 4 : WF == GWF_W4 ? LLJ_GLDS_W4_WN : 2, WM = 8 / WN;
+  static constexpr int WN = BN == 256 ? 4 : WF == GWF_W4 ? kGldsW4WN : 2, WM = 8 / WN;
   static constexpr int MI = 256 / WM / 16, NJ = BN / WN / 16;
   static constexpr size_t SA = 256 * 128;
   // int4 (both forms) at BN 128: the chunk's 4 KiB of W4P codes, waves 4-7 staging a copy (equal DMA
@@ -781,7 +712,10 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
   constexpr int MI = G::MI, NJ = G::NJ, WN = G::WN, NST = G::NST;
   constexpr bool NIB = WF == GWF_W4;  // per-fragment dequant (bf16 128 + q) + row sums
   constexpr bool CVT = G::CVT;        // W4P codes converted once per chunk into a bf16 (q - z) tile
-  constexpr bool FDB = LLJ_GLDS_FDB && BN == 128 && G::NST == 3 && (WF == GWF_BF16 || (CVT && LLJ_W4Z_WAVES == 8));
+  // fragment double buffering (the first K loop below): bf16 and convert-once int4 at 256 x 128
+  constexpr bool FDB = BN == 128 && (WF == GWF_BF16 || CVT);
+  static_assert(!FDB || NST == 3, "fragment double buffering: three stages");
+  static_assert(!CVT || FDB, "convert-once int4 runs only in the fragment-double-buffered loop");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w / WN, wc = w % WN;
@@ -801,16 +735,8 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
   // share it through the XCD's L2) or n fastest (an A row panel stays in L2 while the XCD sweeps the
   // weight columns: the A re-reads go from one per column tile to one per XCD -- the int4 weights are a
   // quarter of the bf16 bytes, so re-reading them per row panel is the cheaper side)
-  constexpr bool NFAST = CVT ? LLJ_GLDS_NFAST_W4Z != 0 : LLJ_GLDS_NFAST_BF16 != 0;
-  // (LLJ_GLDS_GROUPM > 0, A/B: groups of that many row tiles sweep the columns together, m fastest inside)
-  int nb = NFAST ? t % ntiles : t / mtiles, mb = NFAST ? t / ntiles : t % mtiles;
-  if constexpr (LLJ_GLDS_GROUPM > 0) {
-    const int gm = LLJ_GLDS_GROUPM, grp = t / (gm * ntiles), first = grp * gm;
-    const int rows = mtiles - first < gm ? mtiles - first : gm;
-    const int in = t - grp * gm * ntiles;
-    mb = first + in % rows;
-    nb = in / rows;
-  }
+  constexpr bool NFAST = CVT;
+  const int nb = NFAST ? t % ntiles : t / mtiles, mb = NFAST ? t / ntiles : t % mtiles;
   const int m0 = mb * 256, n0 = nb * NOUT;
   float* rs_lds = reinterpret_cast<float*>(smem + NST * G::STAGE);
 
@@ -913,29 +839,25 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
         }
       }
     }
-    if (!CVT || LLJ_W4Z_PRIO) __builtin_amdgcn_s_setprio(1);
+    // the MFMA cluster at raised priority, except convert-once int4: its conversion interleaves with the MFMAs
+    if (!CVT) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[i][j] = mfma_bf16(af[i], bfr[j], acc[i][j]);
-    if (!CVT || LLJ_W4Z_PRIO) __builtin_amdgcn_s_setprio(0);
+    if (!CVT) __builtin_amdgcn_s_setprio(0);
   };
   // convert-once int4: the chunk's codes are converted into 16-B segments 4 s + g of B row
   // 16 tile + column (W4P lane L = 16 s + column of the tile), in the bf16 image's swizzle:
   // bf16(128 + q) - (128 + z) in fp32 is q - z exactly (integral zeros), so the tile holds exact
-  // integers and the scale is applied in the epilogue. LLJ_W4Z_WAVES 8: every wave converts its
-  // own tile w, word pair (lane & 1) of W4P lane lane >> 1, branch-free after its MFMAs (the
-  // scheduler may interleave the VALU with them); 4: waves 0-3 convert tiles 2 w, 2 w + 1 (all four
-  // words of lane L = lane & 31 of tile 2 w + (lane >> 5)), before (LLJ_W4Z_AFTER 0) or after their MFMAs
-  constexpr int CW = LLJ_W4Z_WAVES;
+  // integers and the scale is applied in the epilogue. Every wave converts its own tile w, word
+  // pair (lane & 1) of W4P lane lane >> 1, branch-free in its MFMAs' block (the sched_group pattern
+  // of the K loop interleaves the VALU with them)
   const unsigned char* bf_lds = smem + NST * G::STAGE;
-  const int ctile = CW == 8 ? w : 2 * w + (lane >> 5), cl = CW == 8 ? lane >> 1 : lane & 31, ccol = cl & 15,
-            cs = cl >> 4, cg = CW == 8 ? 2 * (lane & 1) : 0;
+  const int ctile = w, cl = lane >> 1, ccol = cl & 15, cs = cl >> 4, cg = 2 * (lane & 1);
   float zoff = 0.f;  // 128 + zero of this lane's column
-  if constexpr (CVT) {
-    if (CW == 8 || w < 4) zoff = DUAL ? (ctile < 4 ? p.sz : p.sz2)[n0 + 16 * (ctile & 3) + ccol].y : p.sz[n0 + 16 * ctile + ccol].y;
-  }
-  // CW 8, split: the codes read issued before the chunk's fragment reads (asm, no wait; LDS reads
+  if constexpr (CVT) zoff = DUAL ? (ctile < 4 ? p.sz : p.sz2)[n0 + 16 * (ctile & 3) + ccol].y : p.sz[n0 + 16 * ctile + ccol].y;
+  // In the K loop the codes read is issued before the chunk's fragment reads (asm, no wait; LDS reads
   // complete in order, so the compiler's own lgkmcnt waits for the later fragment reads cover it, and
   // the explicit wait below ties the value to it), the conversion after them, in the MFMAs' block
   auto cread = [&](int buf) {
@@ -964,27 +886,18 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
       asm volatile("ds_write_b128 %0, %1" ::"v"(da + (((4 * cs + cg + g4) ^ ((ccol >> 1) & 7)) * 16)), "v"(ov) : "memory");
     }
   };
+  // the prologue's form (chunks 0 and 1): read, wait and convert in one go
   auto convert = [&](int buf, int slot) {
     // the read in asm, with its own wait: read as a plain LDS load, hipcc waits vmcnt(0) for every
     // LDS-DMA in flight first (the next chunks' too), de-pipelining the loop
     const uint32_t ra = (uint32_t)(uintptr_t)(lds_void_t*)(smem + (size_t)buf * G::STAGE + G::SA + 512 * ctile + 16 * cl +
                                                            4 * cg);
-    constexpr int NWD = CW == 8 ? 2 : 4;  // words per lane
-    uint32_t wv4[NWD];
-    if constexpr (CW == 8) {
-      uint2 t;
-      asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(ra) : "memory");
-      wv4[0] = t.x;
-      wv4[1] = t.y;
-    } else {
-      u32x4 t;
-      asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(ra) : "memory");
-      wv4[0] = t[0]; wv4[1] = t[1]; wv4[2] = t[2]; wv4[3] = t[3];
-    }
+    uint2 t;
+    asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(ra) : "memory");
     const uint32_t da = (uint32_t)(uintptr_t)(lds_void_t*)(bf_lds + (size_t)slot * BN * 128 + (16 * ctile + ccol) * 128);
 #pragma unroll
-    for (int g4 = 0; g4 < NWD; ++g4) {
-      const uint32_t wv = wv4[g4];
+    for (int g4 = 0; g4 < 2; ++g4) {
+      const uint32_t wv = g4 ? t.y : t.x;
       uint32_t o[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -998,10 +911,13 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
       asm volatile("ds_write_b128 %0, %1" ::"v"(da + (((4 * cs + cg + g4) ^ ((ccol >> 1) & 7)) * 16)), "v"(ov) : "memory");
     }
   };
-  auto compute = [&](int buf, int slot) {
+  // one chunk of the plain staged loop (bf16 at 256 x 256, per-fragment int4)
+  auto compute = [&](int buf) {
     const unsigned char* Ab = smem + (size_t)buf * G::STAGE;
-    const unsigned char* Bb = CVT ? bf_lds + (size_t)slot * BN * 128 : Ab + G::SA;
-    if constexpr (LLJ_GLDS_PRE && BN == 128) {  // both MFMA steps' fragments read before either's MFMAs
+    const unsigned char* Bb = Ab + G::SA;
+    // 256 x 128 (per-fragment int4): both MFMA steps' fragments read before either's MFMAs (measured
+    // against a read per step on the bf16 window: 35.9 -> 35.4 ms); 256 x 256 tiles read per step
+    if constexpr (BN == 128) {
       bf16x8 af0[MI], bf0[NJ], af1[MI], bf1[NJ];
       frags(Ab, Bb, 0, af0, bf0);
       frags(Ab, Bb, 1, af1, bf1);
@@ -1017,7 +933,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     }
   };
 
-  // ---- K loop, fragment double buffering (LLJ_GLDS_FDB, bf16 and convert-once int4 at 256 x 128): the
+  // ---- K loop, fragment double buffering (bf16 and convert-once int4 at 256 x 128): the
   // fragments of chunk t + 1 are read from LDS while chunk t's MFMAs run (two register sets), so the DMA
   // runs three chunks ahead (every stage issued, past the end with a clamped chunk index: equal DMA
   // counts per wave in every iteration) and each iteration waits for chunk t + 1 instead of t
@@ -1043,14 +959,13 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
       mma(0, cur.a0, cur.b0);
       mma(1, cur.a1, cur.b1);
       if constexpr (CVT) cfinish(ct, t & 1);  // chunk t + 2's tile into chunk t's slot (read in the previous iteration)
-      // the MFMAs interleaved with the next chunk's fragment reads (LLJ_FDB_DSPM per MFMA) and the
-      // conversion's VALU (LLJ_W4Z_VPM per MFMA)
-      if constexpr ((CVT && LLJ_W4Z_IGLP) || LLJ_FDB_DSPM > 0) {
+      // convert-once int4: the conversion's VALU between the MFMAs (1 MFMA, kW4zVPM VALU, ...); the next
+      // chunk's fragment reads are left to the scheduler
+      if constexpr (CVT) {
 #pragma unroll
         for (int q = 0; q < 2 * MI * NJ; ++q) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if constexpr (LLJ_FDB_DSPM > 0) __builtin_amdgcn_sched_group_barrier(0x100, LLJ_FDB_DSPM, 0);
-          if constexpr (CVT && LLJ_W4Z_IGLP) __builtin_amdgcn_sched_group_barrier(0x002, LLJ_W4Z_VPM, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, kW4zVPM, 0);
         }
       }
     };
@@ -1076,19 +991,10 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     }
     wait_vm<0>();  // the clamped stages past the end land before the workgroup's LDS is released
   } else {
-  // ---- K loop: NST - 1 chunks staged ahead
-  if constexpr (CVT) {  // chunk 0's codes first, converted before the loop
-    static_assert(NST == 3, "convert-once int4: three stages");
-    stage_codes(0, 0);
-  }
+  // ---- K loop (bf16 at 256 x 256, per-fragment int4): NST - 1 chunks staged ahead
 #pragma unroll
   for (int c = 0; c < NST - 1; ++c)
     if (c < KC) stage(c, c);
-  if constexpr (CVT) {
-    wait_vm<2 * G::NG>();  // chunk 0's codes (KC >= 2: both groups were issued)
-    __builtin_amdgcn_s_barrier();
-    if (CW == 8 || w < 4) convert(0, 0);
-  }
   int cb = 0;  // buffer of chunk t
   for (int tc = 0; tc < KC; ++tc) {
     if constexpr (NST == 3) {
@@ -1096,37 +1002,16 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     } else {
       wait_vm<0>();
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads (and tile writes) of chunk t - 1 are done
-    __builtin_amdgcn_s_barrier();  // chunk t landed for every wave (CVT: and chunk t + 1's codes); t - 1's buffers are free
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of chunk t - 1 are done
+    __builtin_amdgcn_s_barrier();  // chunk t landed for every wave; t - 1's buffer is free
     if (tc + NST - 1 < KC) stage(cb == 0 ? NST - 1 : cb - 1, tc + NST - 1);
-    if constexpr (CVT && CW == 4 && !LLJ_W4Z_AFTER) {
-      if (tc + 1 < KC && w < 4) convert(cb + 1 == NST ? 0 : cb + 1, (tc + 1) & 1);
-    }
-    if constexpr (CVT && CW == 8 && LLJ_W4Z_SPLIT) {
-      const uint2 ct = cread(cb + 1 == NST ? 0 : cb + 1);
-      compute(cb, tc & 1);
-      cfinish(ct, (tc + 1) & 1);
-      if constexpr (LLJ_W4Z_IGLP) {  // the conversion's VALU between the MFMAs: 1 MFMA, LLJ_W4Z_VPM VALU, ...
-#pragma unroll
-        for (int q = 0; q < 2 * MI * NJ; ++q) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, LLJ_W4Z_VPM, 0);
-        }
-      }
-    } else {
-      compute(cb, tc & 1);
-    }
-    if constexpr (CVT && CW == 4 && LLJ_W4Z_AFTER) {
-      if (tc + 1 < KC && w < 4) convert(cb + 1 == NST ? 0 : cb + 1, (tc + 1) & 1);
-    }
-    // branch-free: past the last chunk it converts the clamped codes into the unused slot
-    if constexpr (CVT && CW == 8 && !LLJ_W4Z_SPLIT) convert(cb + 1 == NST ? 0 : cb + 1, (tc + 1) & 1);
+    compute(cb);
     cb = cb + 1 == NST ? 0 : cb + 1;
   }
   }
 
   // ---- epilogue: lane holds rows m0 + wr * 16 MI + 16 i + 4 g + r, column n0 + wc * 16 NJ + 16 j + row
-  if constexpr (EP == GEP_QKV && LLJ_QKV_LDS && !NIB && BN == 128 && MI <= 4) if ((p.head_size & 7) == 0) {
+  if constexpr (EP == GEP_QKV && !NIB && BN == 128 && MI <= 4) if ((p.head_size & 7) == 0) {
     // QKV through LDS: the tile's bf16 c_attn outputs (model.py:204) go to LDS in the accumulator layout,
     // then every thread takes 8 consecutive columns (4 RoPE pairs: no lane exchange) of one row and
     // stores them as one 16-byte vector -- a tile row is 256 contiguous bytes of q, or of one K / V cache
@@ -1174,7 +1059,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     }
     return;
   }
-  if constexpr (LLJ_GLDS_LDS_EPI && !NIB && !PART && BN == 128 && MI <= 4 &&
+  if constexpr (!NIB && !PART && BN == 128 && MI <= 4 &&
                 (EP == GEP_STORE || EP == GEP_RESID || EP == GEP_SILU_MUL || EP == GEP_SWIGLU))
     if ((p.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0) {
       // the other bf16 epilogues through LDS as well: the tile's bf16 values (y, or the whole SwiGLU product) to
@@ -1317,7 +1202,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     float2 szn = make_float2(1.f, 0.f);
     if constexpr (NIB || CVT) szn = p.sz[n];
     const QkvCol qc = EP == GEP_QKV ? qkv_col(p, nblk, n, Cd) : QkvCol{};
-    constexpr int GI = EP == GEP_QKV ? (MI > 4 ? 1 : LLJ_QKV_GI) : 4;  // row blocks whose operands are in flight together
+    constexpr int GI = EP == GEP_QKV ? (MI > 4 ? 1 : kQkvGI) : 4;  // row blocks whose operands are in flight together
 #pragma unroll
     for (int i0 = 0; i0 < MI; i0 += GI) {
       float2 opv[GI][4];
@@ -1371,11 +1256,11 @@ static int gemm_glds_launch(const GemmParams& p, hipStream_t s) {
 static bool glds_enabled(int wf) {
   const int o = opt(LLJ_OPT_GEMM_GLDS);
   if (o >= 0) return o != 0;
-  return wf == GWF_BF16 ? LLJ_GEMM_GLDS_BF16 != 0 : LLJ_GEMM_GLDS_W4 != 0;
+  return wf == GWF_BF16 ? kGldsBf16 : kGldsW4;
 }
 
 // 256 x 256 or 256 x 128 tiles: the shape with the fewer tile-time units over the CUs (waves of
-// tiles rounded up, a 256 x 128 tile costing LLJ_GLDS_COST128 % of a 256 x 256 one)
+// tiles rounded up, a 256 x 128 tile costing kGldsCost128 % of a 256 x 256 one)
 template <int WF, int EP>
 static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   int cus = 256;
@@ -1393,7 +1278,7 @@ static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   const long w256 = p.N % 256 == 0 ? (mt * (p.N / 256) + cus - 1) / cus : -1;
   const long w128 = (mt * (p.N / 128) + cus - 1) / cus;
   const int oc = opt(LLJ_OPT_GLDS_COST128);  // A/B and tests: 0 forces 256 x 128, >= 100 prefers 256 x 256
-  const long cost = oc >= 0 ? oc : LLJ_GLDS_COST128;
+  const long cost = oc >= 0 ? oc : kGldsCost128;
   if (w256 > 0 && 100 * w256 <= cost * w128) return gemm_glds_launch<WF, EP, 256>(p, s);
   return gemm_glds_launch<WF, EP, 128>(p, s);
 }
@@ -1423,21 +1308,16 @@ static int splitk_plan(int wfmt, int M, int N, int K, int* kcs_out);
 
 // option LLJ_OPT_GEMM_W4Z (LLJ_GEMM_W4Z) 1 / 0: int4 with integral zeros (LLJ_WF_ZINT) in the
 // convert-once LDS-DMA kernel / in the int4 default kernel
-#ifndef LLJ_GEMM_W4Z
-#define LLJ_GEMM_W4Z 1
-#endif
-#ifndef LLJ_GEMM_SPLITK
-#define LLJ_GEMM_SPLITK 1  // split-K residual GEMMs for few row tiles (llj_gemm_resid_ws)
-#endif
+constexpr bool kGemmW4z = true;  // the option's default
 static bool w4z_enabled() {
   const int o = opt(LLJ_OPT_GEMM_W4Z);
-  return o >= 0 ? o != 0 : LLJ_GEMM_W4Z != 0;
+  return o >= 0 ? o != 0 : kGemmW4z;
 }
 
 static int splitk_plan(int wfmt, int M, int N, int K, int* kcs_out) {
   const bool w4z = wfmt == (GWF_W4 | LLJ_WF_ZINT) && w4z_enabled();
   const bool bf = wfmt == GWF_BF16 && glds_enabled(GWF_BF16);
-  if ((!w4z && !bf) || M < 256 || N % 128 || K % 128 || K < 1024 || !LLJ_GEMM_SPLITK) return 0;
+  if ((!w4z && !bf) || M < 256 || N % 128 || K % 128 || K < 1024) return 0;
   int cus = 256;
   {
     int dev = 0;
@@ -1472,7 +1352,7 @@ static int gemm_run(int wfmt, GemmParams& p, void* stream) {
     if (!p.sz) return LLJ_EINVAL;
     if (zint && p.M >= 256 && w4z_enabled()) return gemm_glds_launch<GWF_W4Z, EP, 128>(p, s);
     if (p.M >= 256 && p.K % 128 == 0 && glds_enabled(GWF_W4)) return gemm_glds_run<GWF_W4, EP>(p, s);
-    if (LLJ_GEMM_BM256_W4 && p.M >= 256) return gemm_launch<GWF_W4, EP, 256>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_W4, EP, 256>(p, s);
     return gemm_launch<GWF_W4, EP>(p, s);
   }
   if (wfmt == GWF_W8) return p.sz ? gemm_launch<GWF_W8, EP>(p, s) : LLJ_EINVAL;
@@ -1482,13 +1362,13 @@ static int gemm_run(int wfmt, GemmParams& p, void* stream) {
   }
   if (wfmt == GWF_BF16) {
     if (p.M >= 256 && glds_enabled(GWF_BF16)) return gemm_glds_run<GWF_BF16, EP>(p, s);
-    if (LLJ_GEMM_BM256 && p.M >= 256) return gemm_launch<GWF_BF16, EP, 256>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_BF16, EP, 256>(p, s);
     return gemm_launch<GWF_BF16, EP>(p, s);
   }
   if (wfmt == GWF_I8) {
     if (!p.sz || !p.i8ws || p.K % 128) return LLJ_EINVAL;
     if (!p.ao16 != !p.w16 || (p.ao16 && (p.kpad < 64 || p.kpad % 64))) return LLJ_EINVAL;
-    if (LLJ_GEMM_BM256_I8 && p.M >= 256) return gemm_launch<GWF_I8, EP, 256>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_I8, EP, 256>(p, s);
     return gemm_launch<GWF_I8, EP>(p, s);
   }
   return LLJ_EINVAL;
@@ -1581,15 +1461,12 @@ __global__ __launch_bounds__(256) void gemm_swiglu_reduce_kernel(const float* __
   *reinterpret_cast<uint2*>(h + (size_t)m * ldh + n) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
 }
 
-#ifndef LLJ_GEMM_SWIGLU_TAIL
-#define LLJ_GEMM_SWIGLU_TAIL 1  // the dual SwiGLU pass's partial last wave of tiles as split-K halves
-#endif
 // The dual SwiGLU pass over (row tiles) x (H / 64 column tiles): when the tiles leave a partial last wave
 // over the CUs, its column tiles (tc of them, at the right end) run as two K halves -- twice the
 // workgroups at half the length, fitting one wave -- and the full-K launch keeps only whole waves.
 // Returns the tail's column tiles (0: no split), kcs = its 64-deep chunks per half.
 static int swiglu_tail_plan(int M, int H, int K, int* kcs_out) {
-  if (!LLJ_GEMM_SWIGLU_TAIL || M < 256 || H % 64 || K % 128 || K / 64 < 16) return 0;
+  if (M < 256 || H % 64 || K % 128 || K / 64 < 16) return 0;
   int cus = 256;
   {
     int dev = 0;

@@ -75,9 +75,6 @@ constexpr int kSSlot = 8 * kSRow;
 __host__ __device__ constexpr bool am_stream(int am) { return am == AM_STREAM || am == AM_SNORM; }
 // AM_I8Q per-wave ring slot: the quantized rows (8 x 144 B) then, for chunks with outlier columns,
 // those columns' f16(A) of the 8 rows, column-major (128 x 16 B; only outlier columns written / read)
-#ifndef LLJ_I8Q_FAST
-#define LLJ_I8Q_FAST 1  // AM_I8Q: 1 quant8_fast for rows with SCA >= 1/64, 0 quant8f always
-#endif
 constexpr int kQRow = 144;
 constexpr int kQSlotBytes = 8 * kQRow + 128 * 32;  // AM_I8Q: + the outlier columns' f16(A) as fp32 (32 B per column)
 constexpr int kQSlotBytesS = 8 * kQRow;            // AM_I8S: the int8 rows only
@@ -130,9 +127,6 @@ struct GemvParams {
   int asplit;
 };
 constexpr int kNstRows = 16;
-#ifndef LLJ_SACC_NORM
-#define LLJ_SACC_NORM 0  // 7B bs=8 hand-off: 1.877 -> 1.800 ms, bs=2: 1.339 -> 1.353 (the hand-off runs at bs=2 only)
-#endif
 
 // ------------------------------------------------------------------------------------
 // Stage A rows [0, M) into LDS (row stride K + 8 elements; MFMA lanes of rows >= M read row 0
@@ -256,13 +250,10 @@ __device__ __forceinline__ int kofs(int t, int grp) {
 constexpr int kSideChunk = 256;
 // speculative list entries per thread: 8 (4 waves) / 32 (8 waves) per k-block, so ~300 random
 // outlier columns of the down projection's input (9.4 per k-block on average) stay on the fast path
-#ifndef LLJ_I8_SPE
-#define LLJ_I8_SPE 0  // 0: 1 (4 waves, K = 4096) / 2 (8 waves, K = 11008); else that many per thread (A/B)
-#endif
 // (A/B on one box, profiles/r03_c3_side_fastpath.json: each extra entry costs ~0.6 us per call at few
 // outliers; at ~300 columns two entries save 6.5 us on the 8-wave down projection)
 template <int NW>
-constexpr int kSpE = LLJ_I8_SPE ? LLJ_I8_SPE : (NW == 4 ? 1 : 2);
+constexpr int kSpE = NW == 4 ? 1 : 2;  // 1 (4 waves, K = 4096) / 2 (8 waves, K = 11008)
 template <int NW>
 __device__ void i8_side_tile(const GemvParams& p, const int8_t* CB, const float* SCB, int n0, float* part,
                              unsigned char* stage, int cnt_lane, const int (&spk)[kSpE<NW>]) {
@@ -457,35 +448,8 @@ struct APre {
   float ns[2][SR];  // 2 partials per thread (scalar loads: a vector-element read of these miscompiled)
 };
 
-#ifndef LLJ_ABAR
-#define LLJ_ABAR 0
-#endif
 #ifndef LLJ_ABL
 #define LLJ_ABL 0  // ablation switches for profiling only (1 no A prologue, 2 no compute, 4 no epilogue, 8 no AM_I8Q side loop, 16 no streamed-A loads, 32 no epilogue stores)
-#endif
-#ifndef LLJ_I8_SIS
-#define LLJ_I8_SIS 1  // int8 A image: in-stream fp16 side product from the prep's aval table (0: after the stream)
-#endif
-#ifndef LLJ_I8_SIS_E
-#define LLJ_I8_SIS_E 2  // outlier entries per chunk loaded with its weights (a k-block with more: side product after the stream)
-#endif
-#ifndef LLJ_I8S
-#define LLJ_I8S 1  // int8 GEMVs with a statistics workspace: stream its quantized rows (AM_I8S) for 2..8 rows
-#endif
-#ifndef LLJ_LOADFENCE
-#define LLJ_LOADFENCE 0  // 1: the weight refills stay where the loop issues them (see the main loop)
-#endif
-#ifndef LLJ_AFRAG
-#define LLJ_AFRAG 1  // 1: a chunk's NSTEP A fragments read together before its MFMAs (0: one read per step)
-#endif
-#ifndef LLJ_PF
-#define LLJ_PF 0  // L2 prefetch distance of the weight stream in chunks (0 off; A/B)
-#endif
-#ifndef LLJ_FLAT_EPI
-#define LLJ_FLAT_EPI 1  // 1: batched-row epilogues spread over every thread of the workgroup (0: per owner lane)
-#endif
-#ifndef LLJ_ROT
-#define LLJ_ROT 0  // 1: each workgroup starts its chunk walk at a rotation (A/B of HBM access spread)
 #endif
 
 // LDS tail (floats) behind the A image / reduction scratch: [0, 8) per-row RMSNorm rstd (int8:
@@ -517,9 +481,10 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   constexpr int QSB = I8Q ? kQSlotBytes : kQSlotBytesS;  // its slot bytes
   constexpr bool ALDS = (I8 && !QRING) || (AM != AM_GLOBAL && !STRM && !QRING);
   // row sums of A for the nibble offset: an extra MFMA against a ones fragment for the global-A
-  // form and for batched norm-fused rows (LLJ_SACC_NORM; the VALU sums + 8 wave reductions of the
-  // prologue sit on its critical path), else summed while the LDS image is written
-  constexpr bool SACC = W4L && (!ALDS || (LLJ_SACC_NORM && AM == AM_NORM && MB > 1));
+  // form, else summed while the LDS image is written (measured against the extra MFMA for batched
+  // norm-fused rows as well, which gave on the 7B hand-off bs=8 1.877 -> 1.800 ms but bs=2 1.339 -> 1.353,
+  // and the hand-off runs at bs=2 only)
+  constexpr bool SACC = W4L && !ALDS;
   constexpr int WV = (WF == WF_W4 || GRP) ? 1 : (WF == WF_BF16 ? 4 : 2);  // 16-B loads per lane per chunk per matrix
   constexpr int NSTEP = I8 ? 2 : 4;
   const int lane = threadIdx.x & 63;
@@ -617,11 +582,14 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   for (int m = 0; m < (I8 ? 8 : 1); ++m) sd[m] = 0.f;
 #pragma unroll
   for (int m = 0; m < (I8 && DUAL ? 8 : 1); ++m) sd2[m] = 0.f;
-  // int8 A image (SIS): the chunk's outlier count and its first LLJ_I8_SIS_E (column, f16(A) rows)
-  // entries of the prep's list / aval table, loaded with the chunk's weights (the workspace layout
-  // from this launch's M and K: valid addresses whatever the header says; used only when `sis`)
-  constexpr bool SIS = I8 && !I8Q && LLJ_I8_SIS && D <= 4;  // (the depth-8 forms: registers)
-  constexpr int SE = SIS ? LLJ_I8_SIS_E : 1;
+  // int8 A image (SIS): the fp16 side product in the stream -- the chunk's outlier count and its first
+  // kSisE (column, f16(A) rows) entries of the prep's list / aval table, loaded with the chunk's weights
+  // (the workspace layout from this launch's M and K: valid addresses whatever the header says; used
+  // only when `sis`)
+  constexpr bool SIS = I8 && !I8Q && D <= 4;  // (the depth-8 forms: registers)
+  // outlier entries per chunk loaded with its weights (a k-block with more: side product after the stream)
+  constexpr int kSisE = 2;
+  constexpr int SE = SIS ? kSisE : 1;
   int scn[SIS ? D : 1], sk[SIS ? D : 1][SE];
   u32x4 sav[SIS ? D : 1][SE];
   bool sis = false;  // uniform: the workspace carries aval and its k-blocks are the chunks
@@ -642,27 +610,12 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
       aptr[h] = p.A + (size_t)(rr < M ? rr : M - 1) * p.lda + 8 * (lane & 15);
     }
   }
-  // chunk of the wave's i-th step: its chunks wave, wave + NW, ... in order, or (LLJ_ROT) started at a
-  // per-workgroup rotation so that the workgroups do not all stream the same chunk offsets together
-  const int rot = LLJ_ROT && nmy > 0 ? uniform((int)(blockIdx.x % (unsigned)nmy)) : 0;
+  // chunk of the wave's i-th step: its chunks wave, wave + NW, ... in order
   auto chunk_of = [&](int i) {
-    int ii = i < nmy ? i : nmy - 1;
-    if (LLJ_ROT) ii = ii + rot >= nmy ? ii + rot - nmy : ii + rot;
+    const int ii = i < nmy ? i : nmy - 1;
     return wave + NW * ii;
   };
   const int vz = (I8Q || SIS) ? vzero() : 0;  // uniform side data stays in VGPRs (common.h vzero)
-  // L2 prefetch (LLJ_PF > 0): with chunk i's loads, one dword per lane of chunk i + LLJ_PF's weight
-  // blocks (a wave's 64 lanes touch the whole 1 KiB block, so its lines are in L2 when the real
-  // 16-byte loads come): in-flight bytes past the register ring at 1 VGPR per block. The dword is
-  // "used" (an empty asm) when its slot is reloaded, so the compiler counts it in its waits.
-  constexpr int PF = LLJ_PF;
-  uint32_t pfv[PF > 0 ? D : 1][TPW][WV][2];
-#pragma unroll
-  for (int d = 0; d < (PF > 0 ? D : 1); ++d)
-#pragma unroll
-    for (int j = 0; j < TPW; ++j)
-#pragma unroll
-      for (int v = 0; v < WV; ++v) pfv[d][j][v][0] = pfv[d][j][v][1] = 0u;
   auto load = [&](int d, int i) {
     int c = chunk_of(i);
     c = c < 0 ? 0 : (c >= KC ? KC - 1 : c);  // always a valid chunk (loads past the end are unused)
@@ -701,19 +654,6 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
         r1[d][j][v] = __builtin_nontemporal_load(w1[j] + (size_t)c * wstep + vstride * v);
         if (DUAL) r2[d][j][v] = __builtin_nontemporal_load(w2[j] + (size_t)c * wstep + vstride * v);
       }
-    if constexpr (PF > 0) {
-      int cp = i + PF < nmy ? chunk_of(i + PF) : -1;
-      const bool pf_on = cp >= 0;  // (past the wave's last chunk: a re-read of chunk c, an L2 hit)
-      cp = pf_on ? cp : c;
-#pragma unroll
-      for (int j = 0; j < TPW; ++j)
-#pragma unroll
-        for (int v = 0; v < WV; ++v) {
-          asm volatile("" ::"v"(pfv[d][j][v][0]), "v"(pfv[d][j][v][1]));  // the slot's previous prefetch
-          pfv[d][j][v][0] = *reinterpret_cast<const uint32_t*>(w1[j] + (size_t)cp * wstep + vstride * v);
-          if (DUAL) pfv[d][j][v][1] = *reinterpret_cast<const uint32_t*>(w2[j] + (size_t)cp * wstep + vstride * v);
-        }
-    }
     if (!ALDS) {
 #pragma unroll
       for (int t = 0; t < NSTEP; ++t)
@@ -865,8 +805,8 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
       *reinterpret_cast<u32x4*>(slot + (lane >> 4) * kSRow + 8 * (lane & 15)) = x0;
       *reinterpret_cast<u32x4*>(slot + ((lane >> 4) + 4) * kSRow + 8 * (lane & 15)) = x1;
     }
-    // the chunk's A fragments, all read before the first MFMA: one LDS latency per chunk (LLJ_AFRAG;
-    // read per step, a uniform branch between the steps kept every step's read behind a full
+    // the chunk's A fragments, all read before the first MFMA: one LDS latency per chunk (measured
+    // against a read per step: a uniform branch between the steps kept every step's read behind a full
     // lgkmcnt(0) wait -- exposed at one wave per SIMD, the batched forms)
     u32x4 avs[NSTEP];
 #pragma unroll
@@ -887,10 +827,6 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
           acc[j] = mfma_bf16(a, dequant_w4(r1[d][j][0][t], msk, mag), acc[j]);
           if (DUAL) acc2[j] = mfma_bf16(a, dequant_w4(r2[d][j][0][t], msk, mag), acc2[j]);
         }
-        // (a uniform branch; the unconditional form with a zero fragment measured slower: without
-        // the block boundaries the compiler sank the refills to the loop end, 5,243 -> 4,821
-        // tokens/s at bs=8, profiles/r05_ab_bs8.jsonl). LLJ_AFRAG: one branch per chunk, after the steps
-        if (!LLJ_AFRAG && SACC && !p.rowsum) sacc = mfma_bf16(a, ones, sacc);  // else: row sums from the prologue / caller
       } else if constexpr (GRP) {
         const bf16x8 a = __builtin_bit_cast(bf16x8, av);
 #pragma unroll
@@ -910,7 +846,6 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
             acc2[j] = mfma_bf16(a, dequant_w4(r2[d][j][1][t], msk, mag_hi), acc2[j]);
           }
         }
-        if (!LLJ_AFRAG && SACC && !p.rowsum) sacc = mfma_bf16(a, ones, sacc);
       } else if constexpr (WF == WF_BF16) {
         const bf16x8 a = __builtin_bit_cast(bf16x8, av);
 #pragma unroll
@@ -924,7 +859,11 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
         if (DUAL) iacc2 = mfma_i8(a, __builtin_bit_cast(i32x4, r2[d][0][t]), iacc2);
       }
     }
-    if constexpr (LLJ_AFRAG && W4L && SACC) {  // the chunk's A row sums (nibble offset), one uniform branch
+    // the chunk's A row sums (nibble offset), one uniform branch per chunk, after the steps (else: row sums
+    // from the prologue / caller). A branch, not the unconditional form with a zero fragment, which
+    // measured slower: without the block boundaries the compiler sank the refills to the loop end,
+    // 5,243 -> 4,821 tokens/s at bs=8, profiles/r05_ab_bs8.jsonl
+    if constexpr (SACC) {
       if (!p.rowsum) {
 #pragma unroll
         for (int t = 0; t < NSTEP; ++t) sacc = mfma_bf16(__builtin_bit_cast(bf16x8, avs[t]), ones, sacc);
@@ -954,7 +893,7 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   constexpr int RR = MB == 1 ? 1 : 4;
   int e_ps[4] = {0, 0, 0, 0};
   auto issue_pos = [&]() {
-    if constexpr (EP == EP_QKV && !(MB > 1 && LLJ_FLAT_EPI != 0)) {
+    if constexpr (EP == EP_QKV && MB == 1) {  // (batched rows: the flat epilogue loads its own)
 #pragma unroll
       for (int r = 0; r < RR; ++r) {
         const int mm = 4 * grp + r < M ? 4 * grp + r : M - 1;
@@ -982,17 +921,17 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
     }
     // an epilogue load under divergent control flow would put a vmcnt(0) between the
     // row stores (stores count in vmcnt): read the row sums here (the branch is uniform)
-    if (W4L && p.rowsum && !(MB > 1 && LLJ_FLAT_EPI != 0)) {
+    if (W4L && p.rowsum && MB == 1) {
 #pragma unroll
       for (int r = 0; r < RR; ++r) e_rs[r] = p.rowsum[4 * grp + r < M ? 4 * grp + r : M - 1];
     }
   };
-  // flat epilogue (batched rows, LLJ_FLAT_EPI): after the reduction every thread of the workgroup
+  // flat epilogue (batched rows): after the reduction every thread of the workgroup
   // finishes whole output elements -- element e = tid + NT q of the (tile slot j, row m, column c)
   // space, c fastest, so c = tid & 15 = this lane's column `row` in every slot (e_a / e_b
   // apply as loaded) and (j, m) follow from rm = (tid >> 4) + 4 NW q. The per-lane form runs 4 rows
   // per lane on the TPW owner waves and idles the lanes of MFMA rows >= M (half of them at M = 8)
-  constexpr bool FLAT = MB > 1 && LLJ_FLAT_EPI != 0;
+  constexpr bool FLAT = MB > 1;
   constexpr int FQ = FLAT ? (TPW * 16 * 16 + NW * 64 - 1) / (NW * 64) : 1;  // passes for M <= 16
   int f_j[FQ], f_m[FQ], f_ps[FQ];
   bool f_v[FQ];
@@ -1236,9 +1175,6 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   issue_xr();
   issue_flat();
   a_issue_any();
-#if LLJ_ABAR
-  __builtin_amdgcn_s_barrier();  // experiment: every wave's A loads ahead of any weight load
-#endif
   // AM_SNORM: the producer's partial sums of squares, partials q = lane + 64 i (i < kSnQ) of rows
   // 0..7 (two 16-B loads per partial), issued before the weight stream
   // AM_I8Q: the producer's SCA partials of rows 0..7, slot = lane (bits of non-negative floats),
@@ -1296,7 +1232,7 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
       if (m == m0c) qi0 = inv;
       if (m == m1c) qi1 = inv;
     }
-    qfast = LLJ_I8Q_FAST != 0;
+    qfast = true;  // quant8_fast for rows with SCA >= 1/64, else quant8f
 #pragma unroll
     for (int m = 0; m < 8; ++m) qfast = qfast && (m >= M || sv[m] >= 0.015625f);
     float mine = sv[0];  // the epilogue's SCA (tail; rows >= M unused); selects, not a dynamic index
@@ -1384,23 +1320,18 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   // chunk i lives in buffer i % D; after computing it the buffer is refilled with chunk i + D.
   // The steady loop runs while every refill is a real chunk; the peeled tail (< 2D chunks)
   // issues no loads past the last chunk, so nothing is in flight when the epilogue waits.
-  // LLJ_LOADFENCE: an empty asm with a memory clobber after each refill keeps the compiler from
-  // sinking the refills to the end of the unrolled loop body (it did, for register pressure: then
-  // every D-chunk round started with a full memory latency exposed)
   int i0 = 0;
   for (; i0 + 2 * D <= nmy; i0 += D) {
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       compute(d, i0 + d);
       load(d, i0 + d + D);
-      if constexpr (LLJ_LOADFENCE != 0) asm volatile("" ::: "memory");
     }
   }
 #pragma unroll
   for (int d = 0; d < D; ++d) {
     if (i0 + d < nmy) compute(d, i0 + d);
     if (i0 + d + D < nmy) load(d, i0 + d + D);
-    if constexpr (LLJ_LOADFENCE != 0) asm volatile("" ::: "memory");
   }
 #pragma unroll
   for (int d = 0; d < D; ++d)
@@ -1868,7 +1799,7 @@ static int pick_am(int wf, const GemvParams& p) {
   if (wf == WF_I8 && p.i8st) return (p.norm_w || p.M > 8) ? -1 : AM_I8Q;  // handed-over row statistics
   if (wf == WF_I8) {
     if (p.norm_w || !p.i8ws) return -1;
-    if (LLJ_I8S && g_stream_a && p.M >= 2 && p.M <= 8) return AM_I8S;
+    if (g_stream_a && p.M >= 2 && p.M <= 8) return AM_I8S;  // the workspace's quantized rows streamed per chunk
     return lds_fits(wf, p.M, p.K) ? AM_LDS : -1;
   }
   if (g_stream_a && p.M >= (g_stream_a >= 2 ? 1 : 2) && p.M <= 8) {
