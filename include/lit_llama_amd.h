@@ -176,6 +176,48 @@ int llj_norm_linear(int wfmt, const void* x, const void* norm_w, float eps, cons
                     void* out, int ldo, int M, int N, int K, const void* i8ws, int i8_row0, const float* rowsum,
                     const float* nstat, int npart, void* stream);
 
+/* ---------------------------------------------------------------- LLaMA-Adapter v2 Linears
+ * The reference's adapter v2 gives every Linear two learned vectors of out_features and computes
+ *   adapter_scale * (F.linear(x, W) + adapter_bias)                  (lit_llama/adapter_v2.py:28-31).
+ * The entry points below are the ops above with that affine applied to the Linear's own output
+ * inside the same launch, before the epilogue consumes it (RoPE and the KV write, the residual add
+ * and nstat_out, silu * mul, the store): same arguments, plus adapter_scale / adapter_bias, bf16
+ * vectors of N (the SwiGLU form: one pair per Linear, H each). Rounding points are the reference's
+ * on bf16 tensors: the Linear's output, the sum and the product are each rounded to bf16; with
+ * scale 1 and bias 0 the result is bitwise the op above. Both pointers NULL = the op above; one
+ * NULL = LLJ_EINVAL. wfmt 0, 1, 3 and grouped int4; wfmt 2 (LLM.int8) returns LLJ_EINVAL. */
+/* llj_linear with the affine (adapter_v2.py:28-31 for any Linear, M <= 16). */
+int llj_linear_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, const void* bias, void* C, int ldc,
+                  int M, int N, int K, const void* i8ws, int i8_row0, const float* rowsum, void* stream,
+                  const void* adapter_scale, const void* adapter_bias);
+/* llj_norm_qkv_rope with c_attn's affine applied before the q / k / v split, RoPE and the cache
+ * write (adapter_v2.py:28-31 inside adapter.py:117-147). */
+int llj_norm_qkv_rope_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W, const void* sz,
+                         void* q_out, void* kcache, void* vcache, const float* rope, const int* pos, int B, int T,
+                         int C, int n_head, int S, int row0, int rows, const void* i8ws, const float* rowsum,
+                         const float* nstat, int npart, void* stream, const void* adapter_scale,
+                         const void* adapter_bias);
+/* llj_linear_resid with c_proj's affine applied before the residual add; nstat_out holds the sums
+ * of squares of the new x (adapter_v2.py:28-31 inside adapter.py:205-206). */
+int llj_linear_resid_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* x, int ldx, int M,
+                        int N, int K, const void* i8ws, int i8_row0, float* nstat_out, void* stream,
+                        const void* adapter_scale, const void* adapter_bias);
+/* llj_linear_resid_attn (the merged attention partials of one row) with attn.c_proj's affine. */
+int llj_linear_resid_attn_v2(int wfmt, const void* part, int nsplit, int n_head, const void* W, const void* sz,
+                             void* x, int ldx, int N, int K, float* nstat_out, void* stream,
+                             const void* adapter_scale, const void* adapter_bias);
+/* llj_norm_swiglu with c_fc1's pair (1) and c_fc2's pair (2) applied before silu and the product
+ * (adapter_v2.py:28-31 inside model.py:258); all four given or all four NULL. */
+int llj_norm_swiglu_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W1, const void* sz1,
+                       const void* W2, const void* sz2, void* h, int M, int H, int K, const void* i8ws, int i8_row0,
+                       const float* rowsum, const float* nstat, int npart, void* stream, const void* adapter_scale1,
+                       const void* adapter_bias1, const void* adapter_scale2, const void* adapter_bias2);
+/* llj_norm_linear with the affine (ln_f + lm_head, adapter_v2.py:28-31 on adapter.py:269). */
+int llj_norm_linear_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W, const void* sz,
+                       void* out, int ldo, int M, int N, int K, const void* i8ws, int i8_row0, const float* rowsum,
+                       const float* nstat, int npart, void* stream, const void* adapter_scale,
+                       const void* adapter_bias);
+
 /* ---------------------------------------------------------------- prefill GEMMs (many rows)
  * The same Linear layers for M >> 16 rows (a prompt, a perplexity window: LLaMA.forward over
  * T tokens, model.py:84-128), MFMA-tiled 128 x 128 per workgroup with the chunk tiles staged
@@ -222,6 +264,23 @@ int llj_gemm_swiglu_ws(int wfmt, const void* A, int lda, const void* W1, const v
  * with norm_w NULL; model.py:204-228). */
 int llj_gemm_qkv_rope(int wfmt, const void* x, const void* W, const void* sz, void* q_out, void* kcache, void* vcache,
                       const float* rope, const int* pos, int B, int T, int C, int n_head, int S, void* stream);
+/* The four GEMMs above for LLaMA-Adapter v2 Linears (adapter_v2.py:28-31; see "LLaMA-Adapter v2
+ * Linears" above): adapter_scale[n] * (y + adapter_bias[n]), bf16 vectors of N, applied in the tile
+ * epilogue (register-staged and LDS-DMA kernels, the LDS-staged QKV / store / residual epilogues
+ * included) before it consumes y, with the same rounding points as the GEMV forms. wfmt 0 (with and
+ * without LLJ_WF_ZINT), 1, 3 and grouped int4. Both NULL = the op above; one NULL = LLJ_EINVAL. The
+ * split-K and dual-pass forms (llj_gemm_resid_ws, llj_gemm_swiglu, llj_gemm_swiglu_ws) have no affine
+ * form: an adapter v2 model runs llj_gemm_resid_v2 and llj_gemm_linear_v2 + llj_gemm_silu_mul_v2. */
+int llj_gemm_linear_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* C, int ldc, int M, int N,
+                       int K, void* stream, const void* adapter_scale, const void* adapter_bias);
+int llj_gemm_resid_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* x, int ldx, int M, int N,
+                      int K, void* stream, const void* adapter_scale, const void* adapter_bias);
+/* (h holds bf16 of c_fc1's affine output from llj_gemm_linear_v2; the pair here is c_fc2's.) */
+int llj_gemm_silu_mul_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* h, int ldh, int M,
+                         int N, int K, void* stream, const void* adapter_scale, const void* adapter_bias);
+int llj_gemm_qkv_rope_v2(int wfmt, const void* x, const void* W, const void* sz, void* q_out, void* kcache,
+                         void* vcache, const float* rope, const int* pos, int B, int T, int C, int n_head, int S,
+                         void* stream, const void* adapter_scale, const void* adapter_bias);
 /* LLM.int8() prompt rows (Linear8bitLt.forward for any M, reference quantization.py:36-75 over
  * bitsandbytes MatMul8bitLt): the four GEMMs above for CB (N, K) int8 in the I8P tiling and SCB
  * (N) fp32, with i8ws = llj_i8_stats / llj_i8_norm_stats of A (all M rows): int8 MFMA over the
@@ -333,6 +392,13 @@ int llj_g_rmsnorm(const void* x, int ldx, const void* w, float eps, void* y, int
  * (q - zero) * scale in fp32 (quantization.py:250-267, 390-409). */
 int llj_g_linear(int wkind, const void* x, int ldx, int M, int K, const void* W, const float* scales, const float* zeros,
                  int bits, int group, int N, void* y, int ldy, const void* resid, int ldr, int dt, void* stream);
+/* llj_g_linear of an adapter v2 Linear (adapter_v2.py:28-31): adapter_scale[n] * (x[m] . W[n] +
+ * adapter_bias[n]) before the residual add; the vectors (N) are of the activation type. dt 0 rounds
+ * the Linear's output, the sum and the product to bf16, dt 1 evaluates the expression as written.
+ * Both NULL = llj_g_linear; one NULL = LLJ_EINVAL. */
+int llj_g_linear_v2(int wkind, const void* x, int ldx, int M, int K, const void* W, const float* scales,
+                    const float* zeros, int bits, int group, int N, void* y, int ldy, const void* resid, int ldr, int dt,
+                    void* stream, const void* adapter_scale, const void* adapter_bias);
 /* c_attn output qkv (B*T, 3C) -> q_out (B*T, C) with RoPE, k (RoPE) / v into cache slot pos[t] % S
  * (model.py:204-228, 312-329); rope (block_size, hs/2, 2) fp32; head size even. */
 int llj_g_rope_kv(const void* qkv, void* q_out, void* kcache, void* vcache, const float* rope, const int* pos, int B, int T,

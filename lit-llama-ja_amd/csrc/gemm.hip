@@ -94,7 +94,21 @@ struct GemmParams {
   // GEP_PARTIAL: nsplit K slices of kcs 64-deep chunks each (kcs even), fp32 partials [nsplit][M][N]
   float* ws;
   int nsplit, kcs;
+  // adapter v2 (the AFF instantiations): per output column adapter_scale, adapter_bias (bf16, N)
+  const bf16_t* ad_s;
+  const bf16_t* ad_b;
 };
+
+// adapter v2 Linear (reference adapter_v2.py:28-31 on bf16 tensors): adapter_scale * (F.linear(x) +
+// adapter_bias) with the Linear's output, the sum and the product each rounded to bf16; ad = (scale,
+// bias) of the element's column. Applied to the dequantized accumulator before an epilogue consumes it
+// (every epilogue starts by rounding its y to bf16, so scale 1 / bias 0 changes no bit).
+__device__ __forceinline__ float2 gemm_affine_col(const GemmParams& p, int n) {
+  return make_float2(bf2f(p.ad_s[n]), bf2f(p.ad_b[n]));
+}
+__device__ __forceinline__ float gemm_affine(float y, float2 ad) {
+  return round_bf(round_bf(round_bf(y) + ad.y) * ad.x);
+}
 
 // Tile epilogues run in two phases per 16-column block: every element's operand is loaded first
 // (gemm_operand: the residual / fc1 value, or the RoPE pair of the row's position), then each
@@ -226,9 +240,11 @@ constexpr size_t gemm_lds_bytes() {
 }
 
 // BM: rows per tile (128, or 256 for bf16 with 8 waves: 4 row groups x 2 column groups of 64 x 64)
-template <int WF, int EP, int BM = kGBM>
+// AFF: the adapter v2 affine in the epilogue (compile-time: the AFF = false kernels carry nothing of it)
+template <int WF, int EP, int BM = kGBM, bool AFF = false>
 __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   static_assert(BM == kGBM || WF == GWF_BF16 || WF == GWF_I8 || WF == GWF_W4, "256-row tiles: bf16, int8, int4");
+  static_assert(!AFF || WF != GWF_I8, "adapter v2 affine: not on the LLM.int8 GEMMs");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool NIB = WF == GWF_W4 || WF == GWF_W8;  // nibble-coded: offset removed with the A row sums
   constexpr bool GRP = WF == GWF_W4G;                  // grouped int4: dequantized to the weight values
@@ -594,6 +610,8 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
     float2 szn = make_float2(1.f, 0.f);
     if constexpr (NIB) szn = p.sz[n];
     if constexpr (I8) szn.x = reinterpret_cast<const float*>(p.sz)[n];  // SCB
+    float2 adn = make_float2(1.f, 0.f);
+    if constexpr (AFF) adn = gemm_affine_col(p, n);
     const int nblk = n0 + wc * 16 * NJ + 16 * j;  // first column of this 16-column block
     const QkvCol qc = EP == GEP_QKV ? qkv_col(p, nblk, n, Cd) : QkvCol{};
     constexpr int GI = I8 ? (EP == GEP_QKV ? 1 : 2) : 4;  // row blocks whose operands are in flight together (LLM.int8: 3 accumulator sets live)
@@ -621,6 +639,7 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
             y = (float)iacc[i0 + i][j][r] * (sa * szn.x * (1.f / (127.f * 127.f)));
             y = (float)(_Float16)((float)(_Float16)y + sacc[i0 + i][j][r]);
           }
+          if constexpr (AFF) y = gemm_affine(y, adn);
           gemm_store_elem<EP>(p, y, m, n, live, row, Cd, opv[i][r], qrow[EP == GEP_QKV ? i0 + i : 0][r], qc);
         }
       }
@@ -629,9 +648,9 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   }
 }
 
-template <int WF, int EP, int BM = kGBM>
+template <int WF, int EP, int BM = kGBM, bool AFF = false>
 static int gemm_launch(const GemmParams& p, hipStream_t s) {
-  auto kern = gemm_kernel<WF, EP, BM>;
+  auto kern = gemm_kernel<WF, EP, BM, AFF>;
   static bool attr_set = false;  // per instantiation, before any graph capture
   const size_t lds = gemm_lds_bytes<WF, BM>();
   if (!attr_set) {
@@ -697,9 +716,11 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int WF, int EP, int BN>
+template <int WF, int EP, int BN, bool AFF = false>
 __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
   static_assert(WF == GWF_BF16 || WF == GWF_W4 || WF == GWF_W4Z, "LDS-DMA GEMM: bf16 and int4 W4P");
+  static_assert(!AFF || (EP != GEP_SWIGLU && EP != GEP_PARTIAL && EP != GEP_SWIGLU_PART),
+                "adapter v2 affine: the single-weight, whole-K epilogues");
   static_assert(WF != GWF_W4Z || BN == 128, "convert-once int4: 256 x 128 tiles");
   // the dual SwiGLU form: 64 output columns per tile, B rows 0-63 from W1 and 64-127 from W2 (the same
   // columns), wave column group wc holding output columns 32 wc .. + 31 of BOTH (fragments j < NJ / 2
@@ -1024,10 +1045,16 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     for (int j = 0; j < NJ; ++j) {
       const int nl = wc * 16 * NJ + 16 * j + row;
       const float sc = CVT ? p.sz[n0 + nl].x : 1.f;
+      float2 adn = make_float2(1.f, 0.f);
+      if constexpr (AFF) adn = gemm_affine_col(p, n0 + nl);
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Ts[(wr * 16 * MI + 16 * i + 4 * g + r) * TP + nl] = f2bf(sc * acc[i][j][r]);
+        for (int r = 0; r < 4; ++r) {
+          float y = sc * acc[i][j][r];
+          if constexpr (AFF) y = gemm_affine(y, adn);
+          Ts[(wr * 16 * MI + 16 * i + 4 * g + r) * TP + nl] = f2bf(y);
+        }
     }
     __syncthreads();
     const int Cd = p.n_head * p.head_size, seg = tid & 15;
@@ -1075,6 +1102,8 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
         const float s1 = CVT ? p.sz[n0 + nl].x : 1.f;
         float s2 = 1.f;
         if constexpr (DUAL) s2 = p.sz2[n0 + nl].x;
+        float2 adn = make_float2(1.f, 0.f);
+        if constexpr (AFF) adn = gemm_affine_col(p, n0 + nl);
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -1086,6 +1115,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
               o = sl * round_bf(s2 * acc[i][j + NJ / 2][r]);
             } else {
               o = s1 * acc[i][j][r];
+              if constexpr (AFF) o = gemm_affine(o, adn);
             }
             Ts[(wr * 16 * MI + 16 * i + 4 * g + r) * TP + nl] = f2bf(o);
           }
@@ -1201,6 +1231,8 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     const int n = nblk + row;
     float2 szn = make_float2(1.f, 0.f);
     if constexpr (NIB || CVT) szn = p.sz[n];
+    float2 adn = make_float2(1.f, 0.f);
+    if constexpr (AFF) adn = gemm_affine_col(p, n);
     const QkvCol qc = EP == GEP_QKV ? qkv_col(p, nblk, n, Cd) : QkvCol{};
     constexpr int GI = EP == GEP_QKV ? (MI > 4 ? 1 : kQkvGI) : 4;  // row blocks whose operands are in flight together
 #pragma unroll
@@ -1225,6 +1257,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
           float y = acc[i0 + i][j][r];
           if constexpr (NIB) y = szn.x * (y - szn.y * rs_lds[ml]);
           if constexpr (CVT) y = szn.x * y;
+          if constexpr (AFF) y = gemm_affine(y, adn);
           gemm_store_elem<EP>(p, y, m, n, m < M, row, Cd, opv[i][r], qg[i][r], qc);
         }
       }
@@ -1233,9 +1266,9 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
   }
 }
 
-template <int WF, int EP, int BN>
+template <int WF, int EP, int BN, bool AFF = false>
 static int gemm_glds_launch(const GemmParams& p, hipStream_t s) {
-  auto kern = gemm_glds_kernel<WF, EP, BN>;
+  auto kern = gemm_glds_kernel<WF, EP, BN, AFF>;
   static bool attr_set = false;  // per instantiation, before any graph capture
   const size_t lds = GldsGeo<WF, BN>::LDS;
   if (!attr_set) {
@@ -1261,7 +1294,7 @@ static bool glds_enabled(int wf) {
 
 // 256 x 256 or 256 x 128 tiles: the shape with the fewer tile-time units over the CUs (waves of
 // tiles rounded up, a 256 x 128 tile costing kGldsCost128 % of a 256 x 256 one)
-template <int WF, int EP>
+template <int WF, int EP, bool AFF = false>
 static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   int cus = 256;
   {
@@ -1279,8 +1312,8 @@ static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   const long w128 = (mt * (p.N / 128) + cus - 1) / cus;
   const int oc = opt(LLJ_OPT_GLDS_COST128);  // A/B and tests: 0 forces 256 x 128, >= 100 prefers 256 x 256
   const long cost = oc >= 0 ? oc : kGldsCost128;
-  if (w256 > 0 && 100 * w256 <= cost * w128) return gemm_glds_launch<WF, EP, 256>(p, s);
-  return gemm_glds_launch<WF, EP, 128>(p, s);
+  if (w256 > 0 && 100 * w256 <= cost * w128) return gemm_glds_launch<WF, EP, 256, AFF>(p, s);
+  return gemm_glds_launch<WF, EP, 128, AFF>(p, s);
 }
 
 // split-K residual GEMM (few row tiles: a prompt of 256..1024 rows leaves the 4096-column GEMMs at
@@ -1338,7 +1371,7 @@ static int splitk_plan(int wfmt, int M, int N, int K, int* kcs_out) {
   return ns < 2 ? 0 : ns;
 }
 
-template <int EP>
+template <int EP, bool AFF = false>
 static int gemm_run(int wfmt, GemmParams& p, void* stream) {
   const bool zint = (wfmt & LLJ_WF_ZINT) != 0;  // int4 only: every zero is an integer
   wfmt &= ~LLJ_WF_ZINT;
@@ -1347,25 +1380,26 @@ static int gemm_run(int wfmt, GemmParams& p, void* stream) {
   if (EP != GEP_QKV && (!p.C || (p.ldc & 1))) return LLJ_EINVAL;
   // the int4 / bf16 kernels assume an even count of 64-deep chunks (gemm_body's __builtin_assume)
   if ((wfmt == GWF_W4 || wfmt == GWF_BF16) && p.K % 128) return LLJ_EINVAL;
+  if (AFF && (!p.ad_s || !p.ad_b)) return LLJ_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (wfmt == GWF_W4) {
     if (!p.sz) return LLJ_EINVAL;
-    if (zint && p.M >= 256 && w4z_enabled()) return gemm_glds_launch<GWF_W4Z, EP, 128>(p, s);
-    if (p.M >= 256 && p.K % 128 == 0 && glds_enabled(GWF_W4)) return gemm_glds_run<GWF_W4, EP>(p, s);
-    if (p.M >= 256) return gemm_launch<GWF_W4, EP, 256>(p, s);
-    return gemm_launch<GWF_W4, EP>(p, s);
+    if (zint && p.M >= 256 && w4z_enabled()) return gemm_glds_launch<GWF_W4Z, EP, 128, AFF>(p, s);
+    if (p.M >= 256 && p.K % 128 == 0 && glds_enabled(GWF_W4)) return gemm_glds_run<GWF_W4, EP, AFF>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_W4, EP, 256, AFF>(p, s);
+    return gemm_launch<GWF_W4, EP, kGBM, AFF>(p, s);
   }
-  if (wfmt == GWF_W8) return p.sz ? gemm_launch<GWF_W8, EP>(p, s) : LLJ_EINVAL;
+  if (wfmt == GWF_W8) return p.sz ? gemm_launch<GWF_W8, EP, kGBM, AFF>(p, s) : LLJ_EINVAL;
   if ((wfmt & 0xff) == GWF_W4G) {  // grouped int4: group size (128-deep chunks) in the bits above
     p.gch = wfmt >> 8;
-    return (p.sz && p.gch >= 1 && p.K % 128 == 0) ? gemm_launch<GWF_W4G, EP>(p, s) : LLJ_EINVAL;
+    return (p.sz && p.gch >= 1 && p.K % 128 == 0) ? gemm_launch<GWF_W4G, EP, kGBM, AFF>(p, s) : LLJ_EINVAL;
   }
   if (wfmt == GWF_BF16) {
-    if (p.M >= 256 && glds_enabled(GWF_BF16)) return gemm_glds_run<GWF_BF16, EP>(p, s);
-    if (p.M >= 256) return gemm_launch<GWF_BF16, EP, 256>(p, s);
-    return gemm_launch<GWF_BF16, EP>(p, s);
+    if (p.M >= 256 && glds_enabled(GWF_BF16)) return gemm_glds_run<GWF_BF16, EP, AFF>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_BF16, EP, 256, AFF>(p, s);
+    return gemm_launch<GWF_BF16, EP, kGBM, AFF>(p, s);
   }
-  if (wfmt == GWF_I8) {
+  if constexpr (!AFF) if (wfmt == GWF_I8) {
     if (!p.sz || !p.i8ws || p.K % 128) return LLJ_EINVAL;
     if (!p.ao16 != !p.w16 || (p.ao16 && (p.kpad < 64 || p.kpad % 64))) return LLJ_EINVAL;
     if (p.M >= 256) return gemm_launch<GWF_I8, EP, 256>(p, s);
@@ -1584,6 +1618,51 @@ int llj_gemm_qkv_rope(int wfmt, const void* x, const void* W, const void* sz, vo
   p.n_head = n_head; p.head_size = C / n_head; p.S = S; p.T = T;
   if (p.head_size & 1 || C % 16) return LLJ_EINVAL;
   return gemm_run<GEP_QKV>(wfmt, p, stream);
+}
+
+// ---- adapter v2 (reference adapter_v2.py:28-31): the four GEMMs with adapter_scale[n] * (y + adapter_bias[n])
+// (bf16 vectors of N) applied in the tile epilogue before it consumes y. A NULL pair is the op above;
+// wfmt 0 (with and without LLJ_WF_ZINT), 1, 3 and grouped int4.
+int llj_gemm_linear_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* C, int ldc, int M, int N,
+                       int K, void* stream, const void* adapter_scale, const void* adapter_bias) {
+  if (!adapter_scale && !adapter_bias) return llj_gemm_linear(wfmt, A, lda, W, sz, C, ldc, M, N, K, stream);
+  GemmParams p{};
+  p.A = (const bf16_t*)A; p.lda = lda; p.M = M; p.N = N; p.K = K; p.W = W; p.sz = (const float2*)sz;
+  p.C = (bf16_t*)C; p.ldc = ldc; p.ad_s = (const bf16_t*)adapter_scale; p.ad_b = (const bf16_t*)adapter_bias;
+  return gemm_run<GEP_STORE, true>(wfmt, p, stream);
+}
+
+int llj_gemm_resid_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* x, int ldx, int M, int N,
+                      int K, void* stream, const void* adapter_scale, const void* adapter_bias) {
+  if (!adapter_scale && !adapter_bias) return llj_gemm_resid(wfmt, A, lda, W, sz, x, ldx, M, N, K, stream);
+  GemmParams p{};
+  p.A = (const bf16_t*)A; p.lda = lda; p.M = M; p.N = N; p.K = K; p.W = W; p.sz = (const float2*)sz;
+  p.C = (bf16_t*)x; p.ldc = ldx; p.ad_s = (const bf16_t*)adapter_scale; p.ad_b = (const bf16_t*)adapter_bias;
+  return gemm_run<GEP_RESID, true>(wfmt, p, stream);
+}
+
+int llj_gemm_silu_mul_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* h, int ldh, int M,
+                         int N, int K, void* stream, const void* adapter_scale, const void* adapter_bias) {
+  if (!adapter_scale && !adapter_bias) return llj_gemm_silu_mul(wfmt, A, lda, W, sz, h, ldh, M, N, K, stream);
+  GemmParams p{};
+  p.A = (const bf16_t*)A; p.lda = lda; p.M = M; p.N = N; p.K = K; p.W = W; p.sz = (const float2*)sz;
+  p.C = (bf16_t*)h; p.ldc = ldh; p.ad_s = (const bf16_t*)adapter_scale; p.ad_b = (const bf16_t*)adapter_bias;
+  return gemm_run<GEP_SILU_MUL, true>(wfmt, p, stream);
+}
+
+int llj_gemm_qkv_rope_v2(int wfmt, const void* x, const void* W, const void* sz, void* q_out, void* kcache,
+                         void* vcache, const float* rope, const int* pos, int B, int T, int C, int n_head, int S,
+                         void* stream, const void* adapter_scale, const void* adapter_bias) {
+  if (!adapter_scale && !adapter_bias)
+    return llj_gemm_qkv_rope(wfmt, x, W, sz, q_out, kcache, vcache, rope, pos, B, T, C, n_head, S, stream);
+  if (B < 1 || T < 1 || n_head < 1 || C % n_head || S < 1 || !pos || !rope) return LLJ_EINVAL;
+  GemmParams p{};
+  p.A = (const bf16_t*)x; p.lda = C; p.M = B * T; p.N = 3 * C; p.K = C; p.W = W; p.sz = (const float2*)sz;
+  p.q_out = (bf16_t*)q_out; p.kcache = (bf16_t*)kcache; p.vcache = (bf16_t*)vcache; p.rope = rope; p.pos = pos;
+  p.n_head = n_head; p.head_size = C / n_head; p.S = S; p.T = T;
+  p.ad_s = (const bf16_t*)adapter_scale; p.ad_b = (const bf16_t*)adapter_bias;
+  if (p.head_size & 1 || C % 16) return LLJ_EINVAL;
+  return gemm_run<GEP_QKV, true>(wfmt, p, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // C-ABI entry points of the weight-streaming GEMV family (device code: gemv_impl.h; the
-// per-format instantiations: gemv_w4.hip, gemv_bf16.hip, gemv_w8.hip, gemv_i8.hip).
+// per-format instantiations: gemv_w4.hip, gemv_bf16.hip, gemv_w8.hip, gemv_i8.hip, gemv_w4g.hip; their
+// adapter v2 forms: gemv_aff_*.hip).
 #include "gemv_impl.h"
 
 namespace llj {
@@ -9,6 +10,15 @@ int g_stream_a = 1;
 
 template <int EP>
 static int dispatch(int wf, int am, const GemvParams& p, hipStream_t s) {
+  if (p.ad_s) {  // adapter v2: the AFF instantiations
+    switch (wf) {
+      case WF_W4: return gemv_launch_aff_w4(am, EP, p, s);
+      case WF_BF16: return gemv_launch_aff_bf16(am, EP, p, s);
+      case WF_W8: return gemv_launch_aff_w8(am, EP, p, s);
+      case WF_W4G: return gemv_launch_aff_w4g(am, EP, p, s);
+    }
+    return LLJ_EINVAL;  // (no LLM.int8 form)
+  }
   switch (wf) {
     case WF_W4: return gemv_launch_w4(am, EP, p, s);
     case WF_BF16: return gemv_launch_bf16(am, EP, p, s);
@@ -36,6 +46,9 @@ static int run(int wfmt, GemvParams& p, void* stream) {
   if (p.nstat && (!p.norm_w || wf == WF_I8 || p.M > kNstRows || p.npart < 1 || p.npart > 2 * kNW * 64))
     return LLJ_EINVAL;
   if (EP == EP_SWIGLU && wf != WF_BF16 && !p.sz2) return LLJ_EINVAL;
+  // adapter v2: scale and bias come as a pair (EP_SWIGLU: both Linears' pairs or neither)
+  if (!p.ad_s != !p.ad_b || !p.ad_s2 != !p.ad_b2 || (EP == EP_SWIGLU ? !p.ad_s != !p.ad_s2 : p.ad_s2 != nullptr))
+    return LLJ_EINVAL;
   const int am = pick_am(wf, p);
   if (am < 0) return LLJ_EINVAL;
   return dispatch<EP>(wf, am, p, (hipStream_t)stream);
@@ -129,6 +142,99 @@ int llj_norm_qkv_rope(int wfmt, const void* x, const void* norm_w, float eps, co
   p.S = S; p.T = T; p.i8ws = i8ws;
   if (p.head_size < 2 || (p.head_size & (p.head_size - 1)) || rows > 8) return LLJ_EINVAL;  // power of two
   return run<EP_QKV>(wfmt, p, stream);
+}
+
+// ---- adapter v2 (reference lit_llama/adapter_v2.py:28-31): the ops above with the Linear's output passed
+// through adapter_scale[n] * (y + adapter_bias[n]) (bf16 vectors of N; each step rounded to bf16) before
+// the epilogue consumes it. A NULL pair is the op above. Formats 0, 1, 3 and grouped int4.
+static void set_affine(GemvParams& p, const void* sc, const void* bi, const void* sc2 = nullptr,
+                       const void* bi2 = nullptr) {
+  p.ad_s = (const bf16_t*)sc; p.ad_b = (const bf16_t*)bi; p.ad_s2 = (const bf16_t*)sc2; p.ad_b2 = (const bf16_t*)bi2;
+}
+
+int llj_linear_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, const void* bias, void* C,
+                  int ldc, int M, int N, int K, const void* i8ws, int i8_row0, const float* rowsum, void* stream,
+                  const void* adapter_scale, const void* adapter_bias) {
+  GemvParams p{};
+  p.rowsum = rowsum;
+  p.A = (const bf16_t*)A; p.lda = lda; p.M = M; p.N = N; p.K = K;
+  p.W = W; p.sz = (const float2*)sz; p.bias = (const bf16_t*)bias; p.C = (bf16_t*)C; p.ldc = ldc;
+  p.i8ws = i8ws; p.m0 = i8_row0;
+  set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_STORE>(wfmt, p, stream);
+}
+
+int llj_norm_linear_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W, const void* sz,
+                       void* out, int ldo, int M, int N, int K, const void* i8ws, int i8_row0, const float* rowsum,
+                       const float* nstat, int npart, void* stream, const void* adapter_scale,
+                       const void* adapter_bias) {
+  GemvParams p{};
+  p.rowsum = rowsum;
+  p.nstat = nstat; p.npart = npart;
+  p.A = (const bf16_t*)x; p.lda = K; p.norm_w = (const bf16_t*)norm_w; p.eps = eps; p.M = M; p.N = N; p.K = K;
+  p.W = W; p.sz = (const float2*)sz; p.C = (bf16_t*)out; p.ldc = ldo;
+  p.i8ws = i8ws; p.m0 = i8_row0;
+  set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_STORE>(wfmt, p, stream);
+}
+
+int llj_linear_resid_v2(int wfmt, const void* A, int lda, const void* W, const void* sz, void* x, int ldx, int M,
+                        int N, int K, const void* i8ws, int i8_row0, float* nstat_out, void* stream,
+                        const void* adapter_scale, const void* adapter_bias) {
+  GemvParams p{};
+  p.nstat_out = nstat_out;
+  p.A = (const bf16_t*)A; p.lda = lda; p.M = M; p.N = N; p.K = K;
+  p.W = W; p.sz = (const float2*)sz; p.C = (bf16_t*)x; p.ldc = ldx;
+  p.i8ws = i8ws; p.m0 = i8_row0;
+  set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_RESID>(wfmt, p, stream);
+}
+
+int llj_norm_swiglu_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W1, const void* sz1,
+                       const void* W2, const void* sz2, void* h, int M, int H, int K, const void* i8ws, int i8_row0,
+                       const float* rowsum, const float* nstat, int npart, void* stream, const void* adapter_scale1,
+                       const void* adapter_bias1, const void* adapter_scale2, const void* adapter_bias2) {
+  GemvParams p{};
+  p.rowsum = rowsum;
+  p.nstat = nstat; p.npart = npart;
+  p.A = (const bf16_t*)x; p.lda = K; p.norm_w = (const bf16_t*)norm_w; p.eps = eps; p.M = M; p.N = H; p.K = K;
+  p.W = W1; p.W2 = W2; p.sz = (const float2*)sz1; p.sz2 = (const float2*)sz2; p.C = (bf16_t*)h; p.ldc = H;
+  p.i8ws = i8ws; p.m0 = i8_row0;
+  set_affine(p, adapter_scale1, adapter_bias1, adapter_scale2, adapter_bias2);
+  return run<EP_SWIGLU>(wfmt, p, stream);
+}
+
+int llj_norm_qkv_rope_v2(int wfmt, const void* x, const void* norm_w, float eps, const void* W, const void* sz,
+                         void* q_out, void* kcache, void* vcache, const float* rope, const int* pos, int B, int T,
+                         int C, int n_head, int S, int row0, int rows, const void* i8ws, const float* rowsum,
+                         const float* nstat, int npart, void* stream, const void* adapter_scale,
+                         const void* adapter_bias) {
+  GemvParams p{};
+  p.rowsum = rowsum ? rowsum + row0 : nullptr;
+  p.nstat = nstat ? nstat + row0 : nullptr; p.npart = npart;
+  if (row0 < 0 || rows < 1 || row0 + rows > B * T || n_head < 1 || C % n_head || S < 1) return LLJ_EINVAL;
+  p.A = (const bf16_t*)x + (size_t)row0 * C; p.lda = C; p.norm_w = (const bf16_t*)norm_w; p.eps = eps;
+  p.M = rows; p.m0 = row0; p.N = 3 * C; p.K = C;
+  p.W = W; p.sz = (const float2*)sz; p.q_out = (bf16_t*)q_out; p.kcache = (bf16_t*)kcache;
+  p.vcache = (bf16_t*)vcache; p.rope = rope; p.pos = pos; p.n_head = n_head; p.head_size = C / n_head;
+  p.S = S; p.T = T; p.i8ws = i8ws;
+  if (p.head_size < 2 || (p.head_size & (p.head_size - 1)) || rows > 8) return LLJ_EINVAL;  // power of two
+  set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_QKV>(wfmt, p, stream);
+}
+
+int llj_linear_resid_attn_v2(int wfmt, const void* part, int nsplit, int n_head, const void* W, const void* sz,
+                             void* x, int ldx, int N, int K, float* nstat_out, void* stream,
+                             const void* adapter_scale, const void* adapter_bias) {
+  if (!part || nsplit < 1 || nsplit > kMergeMax || n_head < 1 || K % n_head) return LLJ_EINVAL;
+  GemvParams p{};
+  p.nstat_out = nstat_out;
+  p.apart = (const float*)part; p.asplit = nsplit; p.n_head = n_head; p.head_size = K / n_head;
+  if (p.head_size < 8 || (p.head_size & (p.head_size - 1))) return LLJ_EINVAL;
+  p.A = nullptr; p.lda = K; p.M = 1; p.N = N; p.K = K;
+  p.W = W; p.sz = (const float2*)sz; p.C = (bf16_t*)x; p.ldc = ldx;
+  set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_RESID>(wfmt, p, stream);
 }
 
 // ---- LLM.int8() decode rows with handed-over statistics (i8ws.h kI8StFlags; M <= 8)

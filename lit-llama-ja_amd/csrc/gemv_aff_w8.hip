@@ -1,0 +1,9 @@
+// Adapter v2 instantiations (AFF: per-column scale and bias in the epilogue) of the GEMV kernels for
+// weight format WF_W8 (gemv_impl.h).
+#include "gemv_impl.h"
+
+namespace llj {
+int gemv_launch_aff_w8(int am, int ep, const GemvParams& p, hipStream_t s) {
+  return launch_fmt<WF_W8, true>(am, ep, p, s);
+}
+}  // namespace llj

@@ -125,6 +125,12 @@ struct GemvParams {
   // AM_MERGE: attention partials [(n_head)][asplit][head_size + 4] floats (attention.h kAttPart) of row 0
   const float* apart;
   int asplit;
+  // adapter v2 (AFF instantiations only; reference adapter_v2.py:28-31): per output column
+  // y = adapter_scale[n] * (y + adapter_bias[n]) in bf16; ad_s2 / ad_b2: c_fc2's pair (EP_SWIGLU)
+  const bf16_t* ad_s;
+  const bf16_t* ad_b;
+  const bf16_t* ad_s2;
+  const bf16_t* ad_b2;
 };
 constexpr int kNstRows = 16;
 
@@ -461,9 +467,12 @@ __host__ __device__ constexpr int tail_floats(int nw) { return 8 + 24 * nw; }
 // last one are loaded as a copy of it and never stored): every wave streams its K-chunks of
 // all TPW tiles behind ONE staged A image, so the prologue (activation rows, RMSNorm) runs
 // once per workgroup instead of once per tile. TPW > 1 only for the standalone LDS-A forms.
-template <int WF, int AM, int EP, int NW, int D, int MB, int TPW = 1>
+// AFF: the Linear's output passes through the adapter v2 affine (GemvParams ad_s / ad_b) before the
+// epilogue consumes it -- a compile-time property, so the AFF = false instantiations carry nothing of it.
+template <int WF, int AM, int EP, int NW, int D, int MB, int TPW = 1, bool AFF = false>
 __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, unsigned char* smem) {
   static_assert(TPW == 1 || (WF != WF_I8 && AM != AM_GLOBAL), "multi-tile: LDS-A forms");
+  static_assert(!AFF || WF != WF_I8, "adapter v2 affine: not on the LLM.int8 forms");
   constexpr int TL_RS = 8 + 16 * NW;
   constexpr bool DUAL = (EP == EP_SWIGLU);
   constexpr bool I8 = (WF == WF_I8);
@@ -907,10 +916,20 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
     e_a[j] = e_b[j] = make_float2(1.f, 0.f);
   }
   float e_rs[4] = {0.f, 0.f, 0.f, 0.f};  // caller's row sums (p.rowsum) of rows 4*grp + r
+  // AFF: adapter_scale / adapter_bias of this lane's column in every tile slot (raw bf16; [1]: c_fc2's)
+  bf16_t e_as[AFF ? TPW : 1][2], e_ab[AFF ? TPW : 1][2];
   auto issue_const = [&]() {  // weights-side epilogue operands (never written in a launch)
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
       const int n = nj[j];
+      if constexpr (AFF) {  // nj is a real column in every slot (clamped tile): branch-free
+        e_as[j][0] = p.ad_s[n];
+        e_ab[j][0] = p.ad_b[n];
+        if (DUAL) {
+          e_as[j][1] = p.ad_s2[n];
+          e_ab[j][1] = p.ad_b2[n];
+        }
+      }
       if constexpr (W4L) {
         e_a[j] = p.sz[n];
         if (DUAL) e_b[j] = p.sz2[n];
@@ -1455,6 +1474,20 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
       }
     }
     y += bias;
+    if constexpr (AFF) {
+      // adapter_scale * (F.linear(x) + adapter_bias) on bf16 tensors (adapter_v2.py:28-31): the Linear's
+      // output, the sum and the product each rounded; every epilogue below starts from a bf16 value
+      bf16_t as = e_as[0][0], ab = e_ab[0][0], as2 = e_as[0][DUAL], ab2 = e_ab[0][DUAL];
+#pragma unroll
+      for (int i = 1; i < TPW; ++i) {  // selects, no dynamic register index
+        as = j == i ? e_as[i][0] : as;
+        ab = j == i ? e_ab[i][0] : ab;
+        as2 = j == i ? e_as[i][DUAL] : as2;
+        ab2 = j == i ? e_ab[i][DUAL] : ab2;
+      }
+      y = round_bf(round_bf(round_bf(y) + bf2f(ab)) * bf2f(as));
+      if (DUAL) y2 = round_bf(round_bf(round_bf(y2) + bf2f(ab2)) * bf2f(as2));
+    }
     bool big = false;
     if (EP == EP_QKV) {
       // c_attn output rounded to bf16 (model.py:204), then RoPE in fp32 (model.py:318-329)
@@ -1597,10 +1630,10 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   LLJ_STAMP(5);
 }
 
-template <int WF, int AM, int EP, int NW, int D, int MB, int TPW>
+template <int WF, int AM, int EP, int NW, int D, int MB, int TPW, bool AFF = false>
 __global__ __launch_bounds__(NW * 64) void gemv_kernel(GemvParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  gemv_body<WF, AM, EP, NW, D, MB, TPW>(p, blockIdx.x * TPW, smem);
+  gemv_body<WF, AM, EP, NW, D, MB, TPW, AFF>(p, blockIdx.x * TPW, smem);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1732,10 +1765,10 @@ constexpr int d_of() {
 #ifndef LLJ_DI8Q
 #define LLJ_DI8Q 4  // AM_I8Q: chunks (2 KiB of int8 weights each) in flight per wave (8 spills)
 #endif
-template <int WF, int AM, int EP, int MB, int NW, int TPW>
+template <int WF, int AM, int EP, int MB, int NW, int TPW, bool AFF = false>
 static int launch_t(const GemvParams& p, hipStream_t s) {
   const size_t sm = gemv_smem(WF, AM, p.M, p.K, NW, TPW);
-  auto kern = gemv_kernel<WF, AM, EP, NW, AM == AM_I8Q ? (EP == EP_SWIGLU ? LLJ_DMS : LLJ_DI8Q) : d_of<EP, MB>(), MB, TPW>;
+  auto kern = gemv_kernel<WF, AM, EP, NW, AM == AM_I8Q ? (EP == EP_SWIGLU ? LLJ_DMS : LLJ_DI8Q) : d_of<EP, MB>(), MB, TPW, AFF>;
   static bool attr_set[16] = {};  // per instantiation and device; set before any graph capture
   if (sm > 64 * 1024) {
     int dev = 0;
@@ -1752,42 +1785,42 @@ static int launch_t(const GemvParams& p, hipStream_t s) {
   return 0;
 }
 
-template <int WF, int AM, int EP, int MB, int NW = nw_of<AM>()>
+template <int WF, int AM, int EP, int MB, int NW = nw_of<AM>(), bool AFF = false>
 static int launch_mb(const GemvParams& p, hipStream_t s) {
   if constexpr (tpw_ok<WF, AM>() && MB > 1) {  // M == 1 (MB 1) always one tile: pick_tpw
     // the residual ops (8 chunks in flight) take at most 2 tiles per workgroup (3 and 4 spill;
     // C / 16 tiles need 2 only past 256 CUs' worth: 13B / 30B / 65B)
     const int t = pick_tpw(p.N / 16, p.M);
     switch (EP == EP_RESID && t > 2 ? 2 : t) {
-      case 2: return launch_t<WF, AM, EP, MB, NW, 2>(p, s);
-      case 3: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 3>(p, s); break;
-      case 4: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 4>(p, s); break;
+      case 2: return launch_t<WF, AM, EP, MB, NW, 2, AFF>(p, s);
+      case 3: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 3, AFF>(p, s); break;
+      case 4: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 4, AFF>(p, s); break;
       default: break;
     }
   }
-  return launch_t<WF, AM, EP, MB, NW, 1>(p, s);
+  return launch_t<WF, AM, EP, MB, NW, 1, AFF>(p, s);
 }
 
-template <int WF, int AM, int EP>
+template <int WF, int AM, int EP, bool AFF = false>
 static int launch(const GemvParams& p, hipStream_t s) {
   if constexpr (am_stream(AM) || AM == AM_I8Q || AM == AM_I8S) {  // batched rows only (M <= 8)
     if constexpr (EP == EP_RESID && LLJ_NWR != kNW)
-      if (p.K >= LLJ_NWR_KMIN) return launch_mb<WF, AM, EP, 8, LLJ_NWR>(p, s);
-    if constexpr (EP == EP_SWIGLU && LLJ_NWS != LLJ_NWM) return launch_mb<WF, AM, EP, 8, LLJ_NWS>(p, s);
-    return launch_mb<WF, AM, EP, 8, LLJ_NWM>(p, s);
+      if (p.K >= LLJ_NWR_KMIN) return launch_mb<WF, AM, EP, 8, LLJ_NWR, AFF>(p, s);
+    if constexpr (EP == EP_SWIGLU && LLJ_NWS != LLJ_NWM) return launch_mb<WF, AM, EP, 8, LLJ_NWS, AFF>(p, s);
+    return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF>(p, s);
   } else {
   // the register-staged prologue has an M == 1 class (bs = 1 decode) and an M <= 8 class
   if constexpr (EP == EP_RESID && AM != AM_GLOBAL && LLJ_NWR != kNW) {
     if (p.K >= LLJ_NWR_KMIN) {  // residual ops: 256 workgroups, more waves each
-      if (WF != WF_I8 && p.M == 1) return launch_mb<WF, AM, EP, 1, LLJ_NWR>(p, s);
+      if (WF != WF_I8 && p.M == 1) return launch_mb<WF, AM, EP, 1, LLJ_NWR, AFF>(p, s);
       // one tile per workgroup: an 8-row image of K >= 8192 exceeds the LDS cap, so the multi-tile
       // forms (M >= 7) were unreachable here (and spilled: 256 VGPRs + scratch)
-      return launch_t<WF, AM, EP, 8, LLJ_NWR, 1>(p, s);
+      return launch_t<WF, AM, EP, 8, LLJ_NWR, 1, AFF>(p, s);
     }
   }
-  if (WF != WF_I8 && AM != AM_GLOBAL && p.M == 1) return launch_mb<WF, AM, EP, 1>(p, s);
-  if constexpr (AM != AM_GLOBAL && WF != WF_I8) return launch_mb<WF, AM, EP, 8, LLJ_NWM>(p, s);
-  return launch_mb<WF, AM, EP, 8>(p, s);
+  if (WF != WF_I8 && AM != AM_GLOBAL && p.M == 1) return launch_mb<WF, AM, EP, 1, nw_of<AM>(), AFF>(p, s);
+  if constexpr (AM != AM_GLOBAL && WF != WF_I8) return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF>(p, s);
+  return launch_mb<WF, AM, EP, 8, nw_of<AM>(), AFF>(p, s);
   }
 }
 
@@ -1826,22 +1859,27 @@ int gemv_launch_bf16(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_w8(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_i8(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_w4g(int am, int ep, const GemvParams& p, hipStream_t s);
+// ... and their adapter v2 (AFF) instantiations (gemv_aff_*.hip; no LLM.int8 form)
+int gemv_launch_aff_w4(int am, int ep, const GemvParams& p, hipStream_t s);
+int gemv_launch_aff_bf16(int am, int ep, const GemvParams& p, hipStream_t s);
+int gemv_launch_aff_w8(int am, int ep, const GemvParams& p, hipStream_t s);
+int gemv_launch_aff_w4g(int am, int ep, const GemvParams& p, hipStream_t s);
 
-template <int WF, int AM>
+template <int WF, int AM, bool AFF = false>
 static int launch_ep(int ep, const GemvParams& p, hipStream_t s) {
   switch (ep) {
-    case EP_STORE: return launch<WF, AM, EP_STORE>(p, s);
-    case EP_RESID: return launch<WF, AM, EP_RESID>(p, s);
-    case EP_QKV: return launch<WF, AM, EP_QKV>(p, s);
-    case EP_SWIGLU: return launch<WF, AM, EP_SWIGLU>(p, s);
+    case EP_STORE: return launch<WF, AM, EP_STORE, AFF>(p, s);
+    case EP_RESID: return launch<WF, AM, EP_RESID, AFF>(p, s);
+    case EP_QKV: return launch<WF, AM, EP_QKV, AFF>(p, s);
+    case EP_SWIGLU: return launch<WF, AM, EP_SWIGLU, AFF>(p, s);
   }
   return LLJ_EINVAL;
 }
-template <int WF>
+template <int WF, bool AFF = false>
 static int launch_fmt(int am, int ep, const GemvParams& p, hipStream_t s) {
   if (am == AM_MERGE) {  // the attn.c_proj residual op of one row (llj_linear_resid_attn)
     if constexpr (WF == WF_W4 || WF == WF_BF16 || WF == WF_W8) {
-      if (ep == EP_RESID && p.M == 1 && p.K < LLJ_NWR_KMIN) return launch_mb<WF, AM_MERGE, EP_RESID, 1>(p, s);
+      if (ep == EP_RESID && p.M == 1 && p.K < LLJ_NWR_KMIN) return launch_mb<WF, AM_MERGE, EP_RESID, 1, nw_of<AM_MERGE>(), AFF>(p, s);
     }
     return LLJ_EINVAL;
   }
@@ -1850,11 +1888,11 @@ static int launch_fmt(int am, int ep, const GemvParams& p, hipStream_t s) {
     if (am == AM_I8S) return launch_ep<WF_I8, AM_I8S>(ep, p, s);
     return launch_ep<WF_I8, AM_LDS>(ep, p, s);
   } else {
-    if (am == AM_SNORM) return launch_ep<WF, AM_SNORM>(ep, p, s);
-    if (am == AM_STREAM) return launch_ep<WF, AM_STREAM>(ep, p, s);
-    if (am == AM_NORM) return launch_ep<WF, AM_NORM>(ep, p, s);
-    if (am == AM_LDS) return launch_ep<WF, AM_LDS>(ep, p, s);
-    return launch_ep<WF, AM_GLOBAL>(ep, p, s);
+    if (am == AM_SNORM) return launch_ep<WF, AM_SNORM, AFF>(ep, p, s);
+    if (am == AM_STREAM) return launch_ep<WF, AM_STREAM, AFF>(ep, p, s);
+    if (am == AM_NORM) return launch_ep<WF, AM_NORM, AFF>(ep, p, s);
+    if (am == AM_LDS) return launch_ep<WF, AM_LDS, AFF>(ep, p, s);
+    return launch_ep<WF, AM_GLOBAL, AFF>(ep, p, s);
   }
 }
 

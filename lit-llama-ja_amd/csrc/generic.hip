@@ -66,13 +66,17 @@ __global__ __launch_bounds__(256) void g_rmsnorm_kernel(const T* __restrict__ x,
 // (n, j) at j N + n, 8 / bits codes per byte, code of k = j epb + r at bits r * bits), per-group
 // fp32 scales / zeros (N, G), group = tile_cols (K for -1); the weight element is the Triton path's
 // (q - zero) * scale in fp32 (quantization.py:250-267, 390-409). One wave per output column, lanes
-// over k, up to 8 rows per wave. T: activation (and dense weight) type.
+// over k, up to 8 rows per wave. T: activation (and dense weight) type. AFF (adapter v2, reference
+// adapter_v2.py:28-31): the Linear's output through ad_s[n] * (y + ad_b[n]) before the residual add,
+// every step rounded on the bf16 path, evaluated as written in fp32.
 constexpr int GL_ROWS = 8;
-template <int WK, typename T>
+template <int WK, typename T, bool AFF = false>
 __global__ __launch_bounds__(256) void g_linear_kernel(const T* __restrict__ x, int ldx, int M, int K,
                                                        const void* __restrict__ W, const float* __restrict__ sc,
                                                        const float* __restrict__ zr, int bits, int group, int N,
-                                                       T* __restrict__ y, int ldy, const T* resid, int ldr) {
+                                                       T* __restrict__ y, int ldy, const T* resid, int ldr,
+                                                       const T* __restrict__ ad_s = nullptr,
+                                                       const T* __restrict__ ad_b = nullptr) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -104,6 +108,12 @@ __global__ __launch_bounds__(256) void g_linear_kernel(const T* __restrict__ x, 
     if (lane == r && r < mr) {
       const size_t m = (size_t)(m0 + r);
       float v = rnd<T>(s);
+      if constexpr (AFF) {
+        v = rnd<T>(ldv(ad_s, n) * rnd<T>(v + ldv(ad_b, n)));
+        // fp32: the product is pinned (empty asm) so that it is not contracted with the residual add
+        // into one fma -- the expression is evaluated as written, each operation rounded
+        asm volatile("" : "+v"(v));
+      }
       if (resid) v = ldv(resid, m * ldr + n) + v;
       stv(y, m * ldy + n, v);
     }
@@ -357,6 +367,28 @@ int llj_g_linear(int wkind, const void* x, int ldx, int M, int K, const void* W,
 #define LLJ_GL(WK, T) \
   hipLaunchKernelGGL((g_linear_kernel<WK, T>), grid, dim3(256), 0, s, (const T*)x, ldx, M, K, W, scales, zeros, \
                      WK == 1 ? 16 : bits, WK == 1 ? K : group, N, (T*)y, ldy, (const T*)resid, ldr)
+  if (wkind == 1) LLJ_DT(dt, LLJ_GL(1, bf16_t), LLJ_GL(1, float));
+  else LLJ_DT(dt, LLJ_GL(0, bf16_t), LLJ_GL(0, float));
+#undef LLJ_GL
+  LLJ_CHECK_LAUNCH();
+  return 0;
+}
+
+int llj_g_linear_v2(int wkind, const void* x, int ldx, int M, int K, const void* W, const float* scales,
+                    const float* zeros, int bits, int group, int N, void* y, int ldy, const void* resid, int ldr, int dt,
+                    void* stream, const void* adapter_scale, const void* adapter_bias) {
+  if (!adapter_scale && !adapter_bias)
+    return llj_g_linear(wkind, x, ldx, M, K, W, scales, zeros, bits, group, N, y, ldy, resid, ldr, dt, stream);
+  LLJ_REQUIRE(adapter_scale && adapter_bias);
+  LLJ_REQUIRE(x && W && y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N && (!resid || ldr >= N) && (dt == 0 || dt == 1));
+  LLJ_REQUIRE(wkind == 1 || (wkind == 0 && scales && zeros && (bits == 2 || bits == 4 || bits == 8) && group > 0 &&
+                             K % (8 / bits) == 0));
+  const dim3 grid((N + 3) / 4, (M + GL_ROWS - 1) / GL_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+#define LLJ_GL(WK, T) \
+  hipLaunchKernelGGL((g_linear_kernel<WK, T, true>), grid, dim3(256), 0, s, (const T*)x, ldx, M, K, W, scales, zeros, \
+                     WK == 1 ? 16 : bits, WK == 1 ? K : group, N, (T*)y, ldy, (const T*)resid, ldr,                  \
+                     (const T*)adapter_scale, (const T*)adapter_bias)
   if (wkind == 1) LLJ_DT(dt, LLJ_GL(1, bf16_t), LLJ_GL(1, float));
   else LLJ_DT(dt, LLJ_GL(0, bf16_t), LLJ_GL(0, float));
 #undef LLJ_GL

@@ -1,0 +1,104 @@
+"""Instruction-following generation with a LLaMA-Adapter v2 fine-tuned model on the MI355X path --
+drop-in for the reference's generate/adapter_v2.py (flags 22-32; argparse, as generate.py).
+
+The model is lit_llama.adapter.LLaMA with add_adapter_v2_parameters_to_linear_layers applied while it
+is built (inside the quantization mode, as generate/adapter_v2.py:64-66 does); the pretrained
+checkpoint and the adapter checkpoint (what adapter_v2_state_from_state_dict selects: the v1 prefix and
+gates, every Linear's adapter_scale / adapter_bias, the RMSNorm scales) are loaded one after the other
+with strict=False, the instruction is wrapped in the Alpaca prompt the adapter was trained against, and
+the text after "### Response:" is printed. Decoding is generate.generate: captured-graph decode steps
+with every Linear's scale and bias in the epilogue of its own launch. --quantize llm.int8 is refused
+(lit_llama/adapter_v2.py).
+"""
+from __future__ import annotations
+
+import argparse
+import importlib.util
+import sys
+import time
+from pathlib import Path
+from typing import Optional
+
+import torch
+
+wd = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(wd))
+
+from generate import generate  # noqa: E402  (generate.py next to this directory)
+from lit_llama import HFTokenizer, Tokenizer  # noqa: E402
+from lit_llama.adapter import LLaMA  # noqa: E402
+from lit_llama.adapter_v2 import add_adapter_v2_parameters_to_linear_layers  # noqa: E402
+from lit_llama.checkpoint import read_checkpoint  # noqa: E402
+from lit_llama.utils import EmptyInitOnDevice, llama_model_lookup  # noqa: E402
+
+
+def _v1_cli():
+    """This package's generate/adapter.py, loaded from its file: `generate` on sys.path is generate.py (a
+    module, not a package), so the sibling script cannot be imported by name."""
+    spec = importlib.util.spec_from_file_location("llj_generate_adapter", Path(__file__).with_name("adapter.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_V1 = _v1_cli()
+RESPONSE_MARK, generate_prompt = _V1.RESPONSE_MARK, _V1.generate_prompt  # the same Alpaca prompt as adapter v1
+
+
+def main(prompt: str = "What food do lamas eat?", input: str = "",
+         adapter_path: Path = Path("out/adapter_v2/alpaca/lit-llama-adapter-finetuned.pth"),
+         pretrained_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
+         tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
+         max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8) -> None:
+    """Generates a response to an instruction and an optional input (reference generate/adapter_v2.py:22-96)."""
+    assert adapter_path.is_file(), adapter_path
+    assert pretrained_path.is_file(), pretrained_path
+    assert tokenizer_path.is_file(), tokenizer_path
+    if not torch.cuda.is_available():
+        raise SystemExit("generate/adapter_v2.py runs on a ROCm GPU (MI355X) only")
+    if quantize == "llm.int8":
+        raise SystemExit("generate/adapter_v2.py: adapter v2 parameters on LLM.int8 Linears are not supported "
+                         "(use no quantization, gptq.int4 or gptq.int8)")
+    print("Loading model ...", file=sys.stderr)
+    t0 = time.time()
+    pretrained = read_checkpoint(pretrained_path)
+    adapter = read_checkpoint(adapter_path)
+    name = llama_model_lookup(pretrained)
+    with EmptyInitOnDevice(device=torch.device("cuda"), dtype=torch.bfloat16, quantization_mode=quantize):
+        model = LLaMA.from_name(name)
+        add_adapter_v2_parameters_to_linear_layers(model)
+    model.load_state_dict(pretrained, strict=False)  # 1. the pretrained weights
+    model.load_state_dict(adapter, strict=False)     # 2. the fine-tuned adapter weights
+    del pretrained, adapter
+    print(f"Time to load model: {time.time() - t0:.02f} seconds.", file=sys.stderr)
+    model.eval()
+    tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
+    text = generate_prompt({"instruction": prompt, "input": input})
+    encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
+    prompt_length = encoded.size(0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    y = generate(model, encoded, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=tokenizer.eos_id)
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    model.reset_cache()
+    print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
+    tokens_generated = y.size(0) - prompt_length
+    print(f"\n\nTime for inference: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description="Generates a response to an instruction with a LLaMA-Adapter v2 model.")
+    ap.add_argument("--prompt", default="What food do lamas eat?", help="the instruction (Alpaca style)")
+    ap.add_argument("--input", default="", help="optional input (Alpaca style)")
+    ap.add_argument("--adapter_path", type=Path, default=Path("out/adapter_v2/alpaca/lit-llama-adapter-finetuned.pth"))
+    ap.add_argument("--pretrained_path", type=Path, default=Path("checkpoints/lit-llama/7B/lit-llama.pth"))
+    ap.add_argument("--tokenizer_path", type=Path, default=Path("checkpoints/lit-llama/tokenizer.model"))
+    ap.add_argument("--quantize", default=None, choices=[None, "llm.int8", "gptq.int4", "gptq.int8"])
+    ap.add_argument("--max_new_tokens", type=int, default=100)
+    ap.add_argument("--top_k", type=int, default=200)
+    ap.add_argument("--temperature", type=float, default=0.8)
+    a = ap.parse_args()
+    main(a.prompt, a.input, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
+         a.top_k, a.temperature)

@@ -84,6 +84,19 @@ SIGNATURES = {
     "llj_g_i8_linear": [_P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _I, _P],
     "llj_attention_adapter": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     "llj_adapter_prefix_add": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    # adapter v2: the op of the same name + (adapter_scale, adapter_bias) (SwiGLU: two pairs)
+    "llj_linear_v2": [_I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "llj_norm_qkv_rope_v2": [_I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I,
+                             _P, _P, _P],
+    "llj_linear_resid_v2": [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "llj_linear_resid_attn_v2": [_I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "llj_norm_swiglu_v2": [_I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P],
+    "llj_norm_linear_v2": [_I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P],
+    "llj_gemm_linear_v2": [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "llj_gemm_resid_v2": [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "llj_gemm_silu_mul_v2": [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "llj_gemm_qkv_rope_v2": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "llj_g_linear_v2": [_I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
 }
 
 _lib = None

@@ -229,6 +229,50 @@ def _gspec(lin: nn.Module):
     raise NotImplementedError(f"{type(lin).__name__} has no any-shape kernel")
 
 
+def _affine(lin: nn.Module, dtype=None):
+    """(adapter_scale, adapter_bias) device pointers of a LLaMA-Adapter v2 Linear (lit_llama.adapter_v2;
+    reference adapter_v2.py:28-39), or None for a Linear without them. The kernels read both vectors in
+    the activation type `dtype`."""
+    prm = lin.__dict__.get("_parameters") or {}  # (plain dict reads: a missed Module.__getattr__ raises inside)
+    sc, bi = prm.get("adapter_scale"), prm.get("adapter_bias")
+    if sc is None and bi is None:
+        return None
+    if sc is None or bi is None:
+        raise TypeError(f"{type(lin).__name__} has only one of adapter_scale / adapter_bias")
+    if hasattr(lin, "SCB"):  # Linear8bitLt: the int8 kernels have no affine epilogue
+        raise NotImplementedError("LLaMA-Adapter v2 parameters on an LLM.int8 Linear (Linear8bitLt) are not supported: "
+                                  "the reference's adapter_v2 forward does not run on quantized weights either; use "
+                                  "bf16 / fp32 weights or gptq.int4 / gptq.int8")
+    N = lin.weight.shape[0] if isinstance(lin, nn.Linear) else lin.out_features
+    for t, what in ((sc, "adapter_scale"), (bi, "adapter_bias")):
+        _hip.require_device(t, what)
+        if t.shape != (N,) or not t.is_contiguous():
+            raise TypeError(f"{what} must be a contiguous vector of out_features = {N}, got {tuple(t.shape)}")
+        if t.dtype not in (torch.bfloat16, torch.float32) or (dtype is not None and t.dtype != dtype):
+            raise TypeError(f"{what} is {t.dtype} on a model computing in {dtype}: cast the model as a whole "
+                            "(model.to(dtype)) after add_adapter_v2_parameters_to_linear_layers")
+    return sc.data_ptr(), bi.data_ptr()
+
+
+def _affine2(a1, a2):
+    """The SwiGLU ops' two (scale, bias) pairs: both of c_fc1 and c_fc2, or neither."""
+    if (a1 is None) != (a2 is None):
+        raise TypeError("c_fc1 and c_fc2 must both carry adapter v2 parameters, or neither")
+    return None if a1 is None else a1 + a2
+
+
+def _lcall(name: str, af, *args) -> None:
+    """The Linear op `name`, or for an adapter v2 Linear (af = its _affine pointers) the entry point
+    `name`_v2: the same arguments + the pointers (include/lit_llama_amd.h)."""
+    if af is None:
+        _hip.call(name, *args)
+    else:
+        _hip.call(name + "_v2", *args, *af)
+
+
+_NO_AFFINE = (None,) * 5
+
+
 def _enable_i8_handoff(w: "_Work", specs) -> None:
     """The LLM.int8 statistics hand-off (see _Work) when every Linear of every layer is LLM.int8."""
     w.i8s = w.y_st is not None and all(s[0] == 2 for layer in specs["layers"] for s in layer)
@@ -440,16 +484,23 @@ class LLaMA(nn.Module):
 
     # -- weight operands, gathered once per call
     def _layer_specs(self):
+        dt = self.act_dtype()
+        # adapter v2 (scale, bias) pointers per Linear, None where a Linear has none (checked first: an
+        # unsupported combination raises before any launch)
+        aff = {"affine": [tuple(_affine(m, dt) for m in (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc1,
+                                                          blk.mlp.c_fc2, blk.mlp.c_proj))
+                          for blk in self.transformer.h],
+               "head_affine": _affine(self.lm_head, dt)}
         if self._generic():
             return {"layers": [tuple(_gspec(m) for m in (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc1,
                                                          blk.mlp.c_fc2, blk.mlp.c_proj))
                                for blk in self.transformer.h],
-                    "head": _gspec(self.lm_head)}
+                    "head": _gspec(self.lm_head), **aff}
         layers = []
         for blk in self.transformer.h:
             layers.append((_wspec(blk.attn.c_attn), _wspec(blk.attn.c_proj), _wspec(blk.mlp.c_fc1),
                            _wspec(blk.mlp.c_fc2), _wspec(blk.mlp.c_proj)))
-        return {"layers": layers, "head": _wspec(self.lm_head)}
+        return {"layers": layers, "head": _wspec(self.lm_head), **aff}
 
     def _i8_prep(self, A, M, K, w, st):
         _hip.call("llj_i8_stats", A.data_ptr(), A.stride(0), M, K, Linear8bitLtThreshold, w.i8ws.data_ptr(), st)
@@ -557,6 +608,7 @@ class LLaMA(nn.Module):
         I8ws = P(w.i8ws)
         for i, blk in enumerate(self.transformer.h):
             (fa, wa, sa), (fp, wp, sp), (f1, w1, s1), (f2, w2, s2), (fd, wd, sd) = specs["layers"][i]
+            aa, ap, a1, a2, ad = specs["affine"][i] if "affine" in specs else _NO_AFFINE
             kc, vc = kv[i]
             if fa == 2:  # LLM.int8: the norm + the activation statistics of all M rows, then the int8 GEMM
                 self._i8_norm_prep(w.x, blk.rms_1, w.xn, M, C, w, st)
@@ -567,10 +619,10 @@ class LLaMA(nn.Module):
             else:
                 _hip.call("llj_rmsnorm_rows", w.x.data_ptr(), blk.rms_1.scale.data_ptr(), blk.rms_1.eps,
                           w.xn.data_ptr(), None, M, C, st)
-                _hip.call("llj_gemm_qkv_rope", _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa), w.q.data_ptr(),
-                          kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, st)
+                _lcall("llj_gemm_qkv_rope", aa, _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa), w.q.data_ptr(),
+                       kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, st)
             self._attention(w, kc, vc, pos, B, T, S, st, i)
-            self._gemm_resid(_gz(fp, blk.attn.c_proj), w.y, wp, sp, w.x, M, C, C, w, st)
+            self._gemm_resid(_gz(fp, blk.attn.c_proj), w.y, wp, sp, w.x, M, C, C, w, st, ap)
             if f1 != f2:
                 raise TypeError("c_fc1 and c_fc2 must share a weight format")
             if f1 == 2:
@@ -584,7 +636,8 @@ class LLaMA(nn.Module):
                 _hip.call("llj_rmsnorm_rows", w.x.data_ptr(), blk.rms_2.scale.data_ptr(), blk.rms_2.eps,
                           w.xn.data_ptr(), None, M, C, st)
                 g1, g2 = _gz(f1, blk.mlp.c_fc1), _gz(f2, blk.mlp.c_fc2)
-                if GEMM_SWIGLU and g1 == g2 == _hip.WF_ZINT and M >= 256 and H % 64 == 0:  # both in one pass
+                if (GEMM_SWIGLU and g1 == g2 == _hip.WF_ZINT and M >= 256 and H % 64 == 0
+                        and _affine2(a1, a2) is None):  # both in one pass (no adapter v2 form: two passes)
                     # (a partial last wave of tiles: its columns as two K halves, llj_gemm_swiglu_ws)
                     nb = _hip.lib().llj_gemm_swiglu_ws_bytes(g1, M, H, C)
                     if nb:
@@ -595,14 +648,15 @@ class LLaMA(nn.Module):
                         _hip.call("llj_gemm_swiglu", g1, w.xn.data_ptr(), C, w1.data_ptr(), P(s1), w2.data_ptr(),
                                   P(s2), w.h.data_ptr(), H, M, H, C, st)
                 else:
-                    _hip.call("llj_gemm_linear", g1, w.xn.data_ptr(), C, w1.data_ptr(), P(s1), w.h.data_ptr(), H, M,
-                              H, C, st)
-                    _hip.call("llj_gemm_silu_mul", g2, w.xn.data_ptr(), C, w2.data_ptr(), P(s2), w.h.data_ptr(), H,
-                              M, H, C, st)
-            self._gemm_resid(_gz(fd, blk.mlp.c_proj), w.h, wd, sd, w.x, M, C, H, w, st)
+                    _lcall("llj_gemm_linear", a1, g1, w.xn.data_ptr(), C, w1.data_ptr(), P(s1), w.h.data_ptr(), H, M,
+                           H, C, st)
+                    _lcall("llj_gemm_silu_mul", a2, g2, w.xn.data_ptr(), C, w2.data_ptr(), P(s2), w.h.data_ptr(), H,
+                           M, H, C, st)
+            self._gemm_resid(_gz(fd, blk.mlp.c_proj), w.h, wd, sd, w.x, M, C, H, w, st, ad)
 
-    def _gemm_resid(self, f, A, W, sz, x, M, N, K, w, st):
-        """x += A . W^T for many rows (LLM.int8: the statistics of A first)."""
+    def _gemm_resid(self, f, A, W, sz, x, M, N, K, w, st, af=None):
+        """x += A . W^T for many rows (LLM.int8: the statistics of A first); af: the Linear's adapter v2
+        pointers (_affine) -- such a Linear does not take the split-K form."""
         if f == 2:
             self._i8_prep(A, M, K, w, st)
             ao, (wg,), kp = self._i8_gathered(A, M, K, [(W, sz, N)], w, st)
@@ -610,17 +664,17 @@ class LLaMA(nn.Module):
                       _hip.ptr(ao), _hip.ptr(wg), kp, x.data_ptr(), x.stride(0), M, N, K, st)
         else:
             # few row tiles (256..1024 prompt rows): the K range split over workgroups (llj_gemm_resid_ws)
-            nb = _hip.lib().llj_gemm_resid_ws_bytes(f, M, N, K) if M >= 256 else 0
+            nb = _hip.lib().llj_gemm_resid_ws_bytes(f, M, N, K) if (M >= 256 and af is None) else 0
             if nb:
                 ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
                 _hip.call("llj_gemm_resid_ws", f, A.data_ptr(), A.stride(0), W.data_ptr(), _hip.ptr(sz), x.data_ptr(),
                           x.stride(0), M, N, K, ws.data_ptr(), nb, st)
             else:
-                _hip.call("llj_gemm_resid", f, A.data_ptr(), A.stride(0), W.data_ptr(), _hip.ptr(sz), x.data_ptr(),
-                          x.stride(0), M, N, K, st)
+                _lcall("llj_gemm_resid", af, f, A.data_ptr(), A.stride(0), W.data_ptr(), _hip.ptr(sz), x.data_ptr(),
+                       x.stride(0), M, N, K, st)
 
     @staticmethod
-    def _glinear(spec, A, M, K, N, out, resid, st):
+    def _glinear(spec, A, M, K, N, out, resid, st, af=None):
         kind, W, sc, zr, bits, group = spec
         if kind == 2:  # LLM.int8 (Linear8bitLt._gspec): statistics + int8 / fp16 products on f16(A)
             ws = torch.empty(_hip.lib().llj_g_i8_ws_bytes(M, K), dtype=torch.uint8, device=A.device)
@@ -631,9 +685,9 @@ class LLaMA(nn.Module):
             return
         if kind == 1 and W.dtype != A.dtype:
             raise TypeError(f"dense Linear weight {W.dtype} with {A.dtype} activations")
-        _hip.call("llj_g_linear", kind, A.data_ptr(), A.stride(0), M, K, W.data_ptr(), _hip.ptr(sc), _hip.ptr(zr), bits,
-                  group, N, out.data_ptr(), out.stride(0), None if resid is None else resid.data_ptr(),
-                  0 if resid is None else resid.stride(0), _dt_code(A.dtype), st)
+        _lcall("llj_g_linear", af, kind, A.data_ptr(), A.stride(0), M, K, W.data_ptr(), _hip.ptr(sc), _hip.ptr(zr), bits,
+               group, N, out.data_ptr(), out.stride(0), None if resid is None else resid.data_ptr(),
+               0 if resid is None else resid.stride(0), _dt_code(A.dtype), st)
 
     def _blocks_generic(self, w, specs, kv, pos, B, T, S, st):
         """The blocks on the any-shape kernels (csrc/generic.hip), per layer (model.py:162-175):
@@ -644,10 +698,11 @@ class LLaMA(nn.Module):
         M = B * T
         for i, blk in enumerate(self.transformer.h):
             sa, sp, s1, s2, sd = specs["layers"][i]
+            aa, ap, a1, a2, am = specs["affine"][i] if "affine" in specs else _NO_AFFINE
             kc, vc = kv[i]
             _hip.call("llj_g_rmsnorm", w.x.data_ptr(), C, blk.rms_1.scale.data_ptr(), blk.rms_1.eps, w.xn.data_ptr(), C,
                       M, C, w.dt, st)
-            self._glinear(sa, w.xn, M, C, 3 * C, w.qkv, None, st)
+            self._glinear(sa, w.xn, M, C, 3 * C, w.qkv, None, st, aa)
             _hip.call("llj_g_rope_kv", w.qkv.data_ptr(), w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                       self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, w.dt, st)
             _hip.call("llj_g_attention", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(), pos.data_ptr(),
@@ -655,13 +710,13 @@ class LLaMA(nn.Module):
             ad = self._adapter(i)
             if ad is not None:
                 self._prefix_add(ad, w, M, st)
-            self._glinear(sp, w.y, M, C, C, w.x, w.x, st)
+            self._glinear(sp, w.y, M, C, C, w.x, w.x, st, ap)
             _hip.call("llj_g_rmsnorm", w.x.data_ptr(), C, blk.rms_2.scale.data_ptr(), blk.rms_2.eps, w.xn.data_ptr(), C,
                       M, C, w.dt, st)
-            self._glinear(s1, w.xn, M, C, H, w.a1, None, st)
-            self._glinear(s2, w.xn, M, C, H, w.a2, None, st)
+            self._glinear(s1, w.xn, M, C, H, w.a1, None, st, a1)
+            self._glinear(s2, w.xn, M, C, H, w.a2, None, st, a2)
             _hip.call("llj_g_silu_mul", w.a1.data_ptr(), w.a2.data_ptr(), w.h.data_ptr(), M * H, w.dt, st)
-            self._glinear(sd, w.h, M, H, C, w.x, w.x, st)
+            self._glinear(sd, w.h, M, H, C, w.x, w.x, st, am)
 
     def _blocks(self, w, specs, kv, pos, B, T, S, st):
         cfg = self.config
@@ -675,6 +730,8 @@ class LLaMA(nn.Module):
             return self._blocks_gemm(w, specs, kv, pos, B, T, S, st)
         for i, blk in enumerate(self.transformer.h):
             (fa, wa, sa), (fp, wp, sp), (f1, w1, s1), (f2, w2, s2), (fd, wd, sd) = specs["layers"][i]
+            aa, ap, a1, a2, ad = specs["affine"][i] if "affine" in specs else _NO_AFFINE
+            a12 = _affine2(a1, a2)
             kc, vc = kv[i]
             # 1. rms_1 + c_attn + rope + kv write
             rs = None
@@ -700,9 +757,9 @@ class LLaMA(nn.Module):
             nst = w.nst if (w.hand and i > 0 and fa != 2) else None
             for r0 in range(0, M if src is not None else 0, QKV_ROWS):
                 r = min(QKV_ROWS, M - r0)
-                _hip.call("llj_norm_qkv_rope", fa, src.data_ptr(), nw, blk.rms_1.eps, wa.data_ptr(), P(sa),
-                          w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), rope.data_ptr(), pos.data_ptr(), B, T, C, nh,
-                          S, r0, r, P(w.i8ws), P(rs), P(nst), w.npart, st)
+                _lcall("llj_norm_qkv_rope", aa, fa, src.data_ptr(), nw, blk.rms_1.eps, wa.data_ptr(), P(sa),
+                       w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), rope.data_ptr(), pos.data_ptr(), B, T, C, nh,
+                       S, r0, r, P(w.i8ws), P(rs), P(nst), w.npart, st)
             # 2. attention, 3. c_proj + residual
             if w.i8s and not w.flash:  # y's LLM.int8 statistics from the attention (clears h's block)
                 _hip.call("llj_attention_i8", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(), pos.data_ptr(),
@@ -714,11 +771,11 @@ class LLaMA(nn.Module):
                 # split partials, merged by c_proj (A/B); y is never materialized, so not with a prefix term
                 _hip.call("llj_attention_part", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), pos.data_ptr(), B, T, nh,
                           C // nh, S, w.att_merge, w.att_part.data_ptr(), st)
-                _hip.call("llj_linear_resid_attn", fp, w.att_part.data_ptr(), w.att_merge, nh, wp.data_ptr(), P(sp),
-                          w.x.data_ptr(), C, C, C, P(w.nst) if w.hand else None, st)
+                _lcall("llj_linear_resid_attn", ap, fp, w.att_part.data_ptr(), w.att_merge, nh, wp.data_ptr(), P(sp),
+                       w.x.data_ptr(), C, C, C, P(w.nst) if w.hand else None, st)
             else:
                 self._attention(w, kc, vc, pos, B, T, S, st, i)
-                self._resid(fp, w.y, wp, sp, w.x, M, C, C, w, st, w.nst if w.hand else None)
+                self._resid(fp, w.y, wp, sp, w.x, M, C, C, w, st, w.nst if w.hand else None, ap)
             # 4. rms_2 + fc1/fc2 + silu*mul
             if f1 != f2:
                 raise TypeError("c_fc1 and c_fc2 must share a weight format")
@@ -750,24 +807,24 @@ class LLaMA(nn.Module):
                 continue
             for r0 in range(0, M, step):
                 r = min(step, M - r0)
-                _hip.call("llj_norm_swiglu", f1, src[r0].data_ptr(), nw, blk.rms_2.eps, w1.data_ptr(), P(s1),
-                          w2.data_ptr(), P(s2), w.h[r0].data_ptr(), r, H, C, P(w.i8ws), r0,
-                          None if rs is None else rs[r0].data_ptr(), None if nst is None else nst[r0].data_ptr(),
-                          w.npart, st)
+                _lcall("llj_norm_swiglu", a12, f1, src[r0].data_ptr(), nw, blk.rms_2.eps, w1.data_ptr(), P(s1),
+                       w2.data_ptr(), P(s2), w.h[r0].data_ptr(), r, H, C, P(w.i8ws), r0,
+                       None if rs is None else rs[r0].data_ptr(), None if nst is None else nst[r0].data_ptr(),
+                       w.npart, st)
             # 5. mlp.c_proj + residual
-            self._resid(fd, w.h, wd, sd, w.x, M, C, H, w, st, w.nst if w.hand else None)
+            self._resid(fd, w.h, wd, sd, w.x, M, C, H, w, st, w.nst if w.hand else None, ad)
 
-    def _resid(self, f, A, W, sz, x, M, N, K, w, st, nst=None):
+    def _resid(self, f, A, W, sz, x, M, N, K, w, st, nst=None, af=None):
         """x += A . W^T; with `nst` (the norm hand-off, N / 16 tiles x 16 rows) also the next
-        RMSNorm's partial sums of squares of the new x."""
+        RMSNorm's partial sums of squares of the new x. af: the Linear's adapter v2 pointers (_affine)."""
         if f == 2:
             self._i8_prep(A, M, K, w, st)
         step = I8_ROWS if f == 2 else LIN_ROWS
         for r0 in range(0, M, step):
             r = min(step, M - r0)
-            _hip.call("llj_linear_resid", f, A[r0].data_ptr(), A.stride(0), W.data_ptr(), _hip.ptr(sz),
-                      x[r0].data_ptr(), x.stride(0), r, N, K, _hip.ptr(w.i8ws), r0,
-                      None if nst is None else nst[r0].data_ptr(), st)
+            _lcall("llj_linear_resid", af, f, A[r0].data_ptr(), A.stride(0), W.data_ptr(), _hip.ptr(sz),
+                   x[r0].data_ptr(), x.stride(0), r, N, K, _hip.ptr(w.i8ws), r0,
+                   None if nst is None else nst[r0].data_ptr(), st)
 
     def _head(self, x, M, specs, out, st, w):
         cfg = self.config
@@ -777,9 +834,10 @@ class LLaMA(nn.Module):
             xn = w.xn if M <= w.xn.shape[0] else torch.empty_like(x)
             _hip.call("llj_g_rmsnorm", x.data_ptr(), x.stride(0), ln.scale.data_ptr(), ln.eps, xn.data_ptr(), C, M, C,
                       w.dt, st)
-            self._glinear(specs["head"], xn, M, C, V, out, None, st)
+            self._glinear(specs["head"], xn, M, C, V, out, None, st, specs.get("head_affine"))
             return
         f, W, sz = specs["head"]
+        ah = specs.get("head_affine")
         rs = nst = None
         if f == 2 and w.i8s and I8_NORM_ROWSTATS and x is w.x:  # ln_f + xn's hand-off block
             xn = w.xn
@@ -800,8 +858,8 @@ class LLaMA(nn.Module):
         elif M >= GEMM_MIN_ROWS and _gemm_fmt(f) and C % 128 == 0 and V % 128 == 0:  # many rows: GEMM
             xn = torch.empty_like(x)
             _hip.call("llj_rmsnorm_rows", x.data_ptr(), ln.scale.data_ptr(), ln.eps, xn.data_ptr(), None, M, C, st)
-            _hip.call("llj_gemm_linear", _gz(f, self.lm_head), xn.data_ptr(), C, W.data_ptr(), _hip.ptr(sz),
-                      out.data_ptr(), out.stride(0), M, V, C, st)
+            _lcall("llj_gemm_linear", ah, _gz(f, self.lm_head), xn.data_ptr(), C, W.data_ptr(), _hip.ptr(sz),
+                   out.data_ptr(), out.stride(0), M, V, C, st)
             return
         elif x is w.x and w.hand and f != 2 and len(self.transformer.h) > 0:  # the last mlp.c_proj's partials
             nst = w.nst
@@ -816,10 +874,10 @@ class LLaMA(nn.Module):
             src, nw = x, ln.scale.data_ptr()
         for r0 in range(0, M, QKV_ROWS):
             r = min(QKV_ROWS, M - r0)
-            _hip.call("llj_norm_linear", f, src[r0].data_ptr(), nw, ln.eps, W.data_ptr(), _hip.ptr(sz),
-                      out[r0].data_ptr(), out.stride(0), r, V, C, _hip.ptr(w.i8ws), r0,
-                      None if rs is None else rs[r0].data_ptr(), None if nst is None else nst[r0].data_ptr(),
-                      w.npart, st)
+            _lcall("llj_norm_linear", ah, f, src[r0].data_ptr(), nw, ln.eps, W.data_ptr(), _hip.ptr(sz),
+                   out[r0].data_ptr(), out.stride(0), r, V, C, _hip.ptr(w.i8ws), r0,
+                   None if rs is None else rs[r0].data_ptr(), None if nst is None else nst[r0].data_ptr(),
+                   w.npart, st)
 
 
 Linear8bitLtThreshold = 6.0  # reference quantization.py:45
@@ -860,11 +918,12 @@ class _BlockHost:
         B, T, C = x.shape
         M = B * T
         mods = (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc1, blk.mlp.c_fc2, blk.mlp.c_proj)
+        aff = [tuple(_affine(m, x.dtype) for m in mods)]
         if cfg.kernel_support() is not None or x.dtype == torch.float32:  # the any-shape kernels
-            specs = {"layers": [tuple(_gspec(m) for m in mods)]}
+            specs = {"layers": [tuple(_gspec(m) for m in mods)], "affine": aff}
             w = _Work(cfg, M, x.device, False, generic=True, dtype=x.dtype)
         else:
-            specs = {"layers": [tuple(_wspec(m) for m in mods)]}
+            specs = {"layers": [tuple(_wspec(m) for m in mods)], "affine": aff}
             need_i8 = any(s[0] == 2 for s in specs["layers"][0])
             w = _Work(cfg, M, x.device, need_i8)
         w.x.copy_(x.reshape(M, C))
@@ -944,11 +1003,14 @@ class MLP(nn.Module):
             a1 = torch.empty(M, H, dtype=x.dtype, device=x.device)
             a2 = torch.empty_like(a1)
             out = torch.empty(M, self.c_proj.out_features, dtype=x.dtype, device=x.device)
-            LLaMA._glinear(_gspec(self.c_fc1), x2, M, K, H, a1, None, st)
-            LLaMA._glinear(_gspec(self.c_fc2), x2, M, K, H, a2, None, st)
+            LLaMA._glinear(_gspec(self.c_fc1), x2, M, K, H, a1, None, st, _affine(self.c_fc1, x.dtype))
+            LLaMA._glinear(_gspec(self.c_fc2), x2, M, K, H, a2, None, st, _affine(self.c_fc2, x.dtype))
             _hip.call("llj_g_silu_mul", a1.data_ptr(), a2.data_ptr(), a1.data_ptr(), M * H, _dt_code(x.dtype), st)
-            LLaMA._glinear(_gspec(self.c_proj), a1, M, H, self.c_proj.out_features, out, None, st)
+            LLaMA._glinear(_gspec(self.c_proj), a1, M, H, self.c_proj.out_features, out, None, st,
+                           _affine(self.c_proj, x.dtype))
             return out.view(*x.shape[:-1], out.shape[1])
+        a12 = _affine2(_affine(self.c_fc1, x.dtype), _affine(self.c_fc2, x.dtype))
+        ad = _affine(self.c_proj, x.dtype)
         (f1, w1, s1), (f2, w2, s2), (fd, wd, sd) = _wspec(self.c_fc1), _wspec(self.c_fc2), _wspec(self.c_proj)
         if f1 != f2:
             raise TypeError("c_fc1 and c_fc2 must share a weight format")
@@ -964,16 +1026,16 @@ class MLP(nn.Module):
         step = I8_ROWS if f1 == 2 else QKV_ROWS
         for r0 in range(0, M, step):
             r = min(step, M - r0)
-            _hip.call("llj_norm_swiglu", f1, x2[r0].data_ptr(), None, 0.0, w1.data_ptr(), _hip.ptr(s1), w2.data_ptr(),
-                      _hip.ptr(s2), h[r0].data_ptr(), r, H, K, _hip.ptr(ws), r0, None, None, 0, st)
+            _lcall("llj_norm_swiglu", a12, f1, x2[r0].data_ptr(), None, 0.0, w1.data_ptr(), _hip.ptr(s1), w2.data_ptr(),
+                   _hip.ptr(s2), h[r0].data_ptr(), r, H, K, _hip.ptr(ws), r0, None, None, 0, st)
         out = torch.empty(M, self.c_proj.out_features, dtype=torch.bfloat16, device=x.device)
         if fd == 2:
             _hip.call("llj_i8_stats", h.data_ptr(), H, M, H, Linear8bitLtThreshold, ws.data_ptr(), st)
         step = I8_ROWS if fd == 2 else LIN_ROWS
         for r0 in range(0, M, step):
             r = min(step, M - r0)
-            _hip.call("llj_linear", fd, h[r0].data_ptr(), H, wd.data_ptr(), _hip.ptr(sd), None, out[r0].data_ptr(),
-                      out.stride(0), r, out.shape[1], H, _hip.ptr(ws), r0, None, st)
+            _lcall("llj_linear", ad, fd, h[r0].data_ptr(), H, wd.data_ptr(), _hip.ptr(sd), None, out[r0].data_ptr(),
+                   out.stride(0), r, out.shape[1], H, _hip.ptr(ws), r0, None, st)
         return out.view(*x.shape[:-1], out.shape[1])
 
 

@@ -30,13 +30,16 @@ _DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 ROWS_PER_CALL = 16  # llj_linear handles M <= 16 rows per launch
 
 
-def _linear_rows(wfmt: int, x2: torch.Tensor, W: torch.Tensor, sz, bias, out2: torch.Tensor, N: int, K: int):
+def _linear_rows(wfmt: int, x2: torch.Tensor, W: torch.Tensor, sz, bias, out2: torch.Tensor, N: int, K: int,
+                 af=None):
+    """af: the (adapter_scale, adapter_bias) pointers of a LLaMA-Adapter v2 Linear (model._affine)."""
     s = _hip.stream()
     M = x2.shape[0]
+    name, tail = ("llj_linear", ()) if af is None else ("llj_linear_v2", af)
     for r0 in range(0, M, ROWS_PER_CALL):
         r = min(ROWS_PER_CALL, M - r0)
-        _hip.call("llj_linear", wfmt, x2[r0].data_ptr(), x2.stride(0), W.data_ptr(), _hip.ptr(sz), _hip.ptr(bias),
-                  out2[r0].data_ptr(), out2.stride(0), r, N, K, None, 0, None, s)
+        _hip.call(name, wfmt, x2[r0].data_ptr(), x2.stride(0), W.data_ptr(), _hip.ptr(sz), _hip.ptr(bias),
+                  out2[r0].data_ptr(), out2.stride(0), r, N, K, None, 0, None, s, *tail)
 
 
 def _as_rows(inp: torch.Tensor, K: int) -> torch.Tensor:
@@ -232,20 +235,26 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         if inp.dtype not in (torch.bfloat16, torch.float32):
             raise TypeError(f"ColBlockQuantizedLinear HIP path computes in bfloat16 or float32, got {inp.dtype}")
         K, N = self.in_features, self.out_features
+        af = None
+        if "adapter_scale" in self._parameters:  # adapter v2: scale * (quantized_linear(x) + bias) in the same launch
+            from .model import _affine
+
+            af = _affine(self, inp.dtype)
         if not self._supported() or inp.dtype == torch.float32:  # the any-shape kernel on the reference buffers
             if self.bias is not None:
                 raise NotImplementedError("biased ColBlockQuantizedLinear on the any-shape / fp32 path")
             x2 = inp.reshape(-1, K).contiguous()
             out = torch.empty((x2.shape[0], N), dtype=inp.dtype, device=inp.device)
             kind, qw, sc, zr, bits, group = self._gspec()
-            _hip.call("llj_g_linear", kind, x2.data_ptr(), K, x2.shape[0], K, qw.data_ptr(), sc.data_ptr(), zr.data_ptr(),
-                      bits, group, N, out.data_ptr(), N, None, 0, 0 if inp.dtype == torch.bfloat16 else 1, _hip.stream())
+            _hip.call("llj_g_linear" if af is None else "llj_g_linear_v2", kind, x2.data_ptr(), K, x2.shape[0], K,
+                      qw.data_ptr(), sc.data_ptr(), zr.data_ptr(), bits, group, N, out.data_ptr(), N, None, 0,
+                      0 if inp.dtype == torch.bfloat16 else 1, _hip.stream(), *(af or ()))
             return out.reshape(*inp.shape[:-1], N)
         self._prepare()
         x2 = _as_rows(inp, K)
         out = torch.empty((x2.shape[0], N), dtype=inp.dtype, device=inp.device)
         bias = None if self.bias is None else self.bias.to(torch.bfloat16)
-        _linear_rows(self.wfmt, x2, self.quant_weight, self._sz, bias, out, N, K)
+        _linear_rows(self.wfmt, x2, self.quant_weight, self._sz, bias, out, N, K, af)
         return out.reshape(*inp.shape[:-1], N)
 
 
@@ -411,6 +420,10 @@ class Linear8bitLt(torch.nn.Module):
         _hip.require_device(x, "input")
         if x.dtype not in (torch.bfloat16, torch.float32):
             raise TypeError(f"Linear8bitLt HIP path computes on bfloat16 or float32 input, got {x.dtype}")
+        if "adapter_scale" in self._parameters:  # adapter v2 parameters on an LLM.int8 Linear: NotImplementedError
+            from .model import _affine
+
+            _affine(self)
         # the any-shape LLM.int8 kernels: shapes outside the streaming tiling, and fp32 input (cast to
         # fp16 inside and the result back to fp32, as bitsandbytes' MatMul8bitLt does)
         if self.in_features % 128 or self.out_features % 16 or x.dtype == torch.float32:
