@@ -489,4 +489,9 @@ int llj_stream_read(const void* p, size_t bytes, float* out, int grid, void* str
 #ifdef __cplusplus
 }
 #endif
+
+/* The LoRA entry points (llj_lora_merge and the `*_lora` forms of the ops that produce c_attn's output)
+ * are declared in a header of their own, part of this ABI. */
+#include "lit_llama_amd_lora.h"
+
 #endif /* LIT_LLAMA_AMD_H */

@@ -167,6 +167,27 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(lo, hi);
 }
 
+// LoRA operands of the unmerged c_attn forms (include/lit_llama_amd.h "LoRA"; reference lora.py:310-323):
+// t = the down-projection of the call's rows (row stride ldt), B = lora_B (n_en * N / 3, r) contiguous,
+// mask bit g = output group g (q, k, v) enabled.
+struct LoraArgs {
+  const void* t;
+  int ldt;
+  const void* B;
+  int r;
+  int mask;
+  float scaling;
+};
+// host: 0 = no LoRA operands (the base op), 1 = a complete valid set, -1 = anything else
+inline int lora_args_state(const void* t, int ldt, const void* B, int r, int mask) {
+  if (!t && !B && r == 0) return 0;
+  if (!t || !B || r < 1 || r > 64 || mask < 1 || mask > 7) return -1;
+  int n_en = (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1);
+  return ldt >= r * n_en ? 1 : -1;
+}
+// index of group g among the enabled groups of mask (the slab of lora_A / lora_B it owns)
+__device__ __forceinline__ int lora_slab(int mask, int g) { return __builtin_popcount(mask & ((1 << g) - 1)); }
+
 }  // namespace llj
 
 // Error convention for the C ABI: 0 = ok, otherwise a hipError_t or one of these.

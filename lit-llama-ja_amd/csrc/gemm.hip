@@ -97,6 +97,9 @@ struct GemmParams {
   // adapter v2 (the AFF instantiations): per output column adapter_scale, adapter_bias (bf16, N)
   const bf16_t* ad_s;
   const bf16_t* ad_b;
+  // LoRA (the LORA instantiations of GEP_QKV): the unmerged c_attn's low-rank term, lora.t = the
+  // down-projection of the M rows (bf16, row stride ldt)
+  LoraArgs lora;
 };
 
 // adapter v2 Linear (reference adapter_v2.py:28-31 on bf16 tensors): adapter_scale * (F.linear(x) +
@@ -108,6 +111,31 @@ __device__ __forceinline__ float2 gemm_affine_col(const GemmParams& p, int n) {
 }
 __device__ __forceinline__ float gemm_affine(float y, float2 ad) {
   return round_bf(round_bf(round_bf(y) + ad.y) * ad.x);
+}
+
+// Unmerged LoRA (reference lora.py:310-323 on bf16 tensors) on c_attn's dequantized accumulator, at the
+// point of the affine above: d = bf16(t[m] . B[n']), y = bf16(bf16(y) + bf16(d * scaling)) on the columns
+// of enabled groups, the others unchanged. LoraCol: the column's row of lora_B and its slab's offset in a
+// row of t (row 0 / slab 0 for a disabled column: loaded, not used). m: a row < M (the caller clamps).
+// The sum runs in index order, as in the GEMV epilogue, so both paths give the same bits for the same y.
+struct LoraCol {
+  const bf16_t* b;
+  int toff;
+  bool en;
+};
+__device__ __forceinline__ LoraCol gemm_lora_col(const GemmParams& p, int n, int Cd) {
+  const int region = n / Cd;
+  const bool en = (p.lora.mask >> region) & 1;
+  const int gi = en ? lora_slab(p.lora.mask, region) : 0;
+  const size_t br = en ? (size_t)gi * Cd + (n - region * Cd) : 0;
+  return LoraCol{reinterpret_cast<const bf16_t*>(p.lora.B) + br * p.lora.r, gi * p.lora.r, en};
+}
+__device__ __forceinline__ float gemm_lora(const GemmParams& p, float y, int m, const LoraCol& lc) {
+  const bf16_t* tr = reinterpret_cast<const bf16_t*>(p.lora.t) + (size_t)m * p.lora.ldt + lc.toff;
+  float d = 0.f;
+  for (int i = 0; i < p.lora.r; ++i) d = fmaf(bf2f(tr[i]), bf2f(lc.b[i]), d);
+  const float yl = round_bf(round_bf(y) + round_bf(round_bf(d) * p.lora.scaling));
+  return lc.en ? yl : y;
 }
 
 // Tile epilogues run in two phases per 16-column block: every element's operand is loaded first
@@ -241,8 +269,10 @@ constexpr size_t gemm_lds_bytes() {
 
 // BM: rows per tile (128, or 256 for bf16 with 8 waves: 4 row groups x 2 column groups of 64 x 64)
 // AFF: the adapter v2 affine in the epilogue (compile-time: the AFF = false kernels carry nothing of it)
-template <int WF, int EP, int BM = kGBM, bool AFF = false>
+// LORA (GEP_QKV): the unmerged LoRA term at the same point.
+template <int WF, int EP, int BM = kGBM, bool AFF = false, bool LORA = false>
 __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
+  static_assert(!LORA || (EP == GEP_QKV && WF != GWF_I8 && !AFF), "LoRA: c_attn, not LLM.int8, not with adapter v2");
   static_assert(BM == kGBM || WF == GWF_BF16 || WF == GWF_I8 || WF == GWF_W4, "256-row tiles: bf16, int8, int4");
   static_assert(!AFF || WF != GWF_I8, "adapter v2 affine: not on the LLM.int8 GEMMs");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -612,6 +642,8 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
     if constexpr (I8) szn.x = reinterpret_cast<const float*>(p.sz)[n];  // SCB
     float2 adn = make_float2(1.f, 0.f);
     if constexpr (AFF) adn = gemm_affine_col(p, n);
+    LoraCol lc{};
+    if constexpr (LORA) lc = gemm_lora_col(p, n, Cd);
     const int nblk = n0 + wc * 16 * NJ + 16 * j;  // first column of this 16-column block
     const QkvCol qc = EP == GEP_QKV ? qkv_col(p, nblk, n, Cd) : QkvCol{};
     constexpr int GI = I8 ? (EP == GEP_QKV ? 1 : 2) : 4;  // row blocks whose operands are in flight together (LLM.int8: 3 accumulator sets live)
@@ -640,6 +672,7 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
             y = (float)(_Float16)((float)(_Float16)y + sacc[i0 + i][j][r]);
           }
           if constexpr (AFF) y = gemm_affine(y, adn);
+          if constexpr (LORA) y = gemm_lora(p, y, live ? m : 0, lc);
           gemm_store_elem<EP>(p, y, m, n, live, row, Cd, opv[i][r], qrow[EP == GEP_QKV ? i0 + i : 0][r], qc);
         }
       }
@@ -648,9 +681,9 @@ __global__ __launch_bounds__(2 * BM) void gemm_kernel(GemmParams p) {
   }
 }
 
-template <int WF, int EP, int BM = kGBM, bool AFF = false>
+template <int WF, int EP, int BM = kGBM, bool AFF = false, bool LORA = false>
 static int gemm_launch(const GemmParams& p, hipStream_t s) {
-  auto kern = gemm_kernel<WF, EP, BM, AFF>;
+  auto kern = gemm_kernel<WF, EP, BM, AFF, LORA>;
   static bool attr_set = false;  // per instantiation, before any graph capture
   const size_t lds = gemm_lds_bytes<WF, BM>();
   if (!attr_set) {
@@ -716,8 +749,9 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int WF, int EP, int BN, bool AFF = false>
+template <int WF, int EP, int BN, bool AFF = false, bool LORA = false>
 __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
+  static_assert(!LORA || (EP == GEP_QKV && !AFF), "LoRA: c_attn, not with adapter v2");
   static_assert(WF == GWF_BF16 || WF == GWF_W4 || WF == GWF_W4Z, "LDS-DMA GEMM: bf16 and int4 W4P");
   static_assert(!AFF || (EP != GEP_SWIGLU && EP != GEP_PARTIAL && EP != GEP_SWIGLU_PART),
                 "adapter v2 affine: the single-weight, whole-K epilogues");
@@ -1047,12 +1081,18 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
       const float sc = CVT ? p.sz[n0 + nl].x : 1.f;
       float2 adn = make_float2(1.f, 0.f);
       if constexpr (AFF) adn = gemm_affine_col(p, n0 + nl);
+      LoraCol lc{};
+      if constexpr (LORA) lc = gemm_lora_col(p, n0 + nl, p.n_head * p.head_size);
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float y = sc * acc[i][j][r];
           if constexpr (AFF) y = gemm_affine(y, adn);
+          if constexpr (LORA) {
+            const int m = m0 + wr * 16 * MI + 16 * i + 4 * g + r;
+            y = gemm_lora(p, y, m < M ? m : 0, lc);
+          }
           Ts[(wr * 16 * MI + 16 * i + 4 * g + r) * TP + nl] = f2bf(y);
         }
     }
@@ -1233,6 +1273,8 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
     if constexpr (NIB || CVT) szn = p.sz[n];
     float2 adn = make_float2(1.f, 0.f);
     if constexpr (AFF) adn = gemm_affine_col(p, n);
+    LoraCol lc{};
+    if constexpr (LORA) lc = gemm_lora_col(p, n, Cd);
     const QkvCol qc = EP == GEP_QKV ? qkv_col(p, nblk, n, Cd) : QkvCol{};
     constexpr int GI = EP == GEP_QKV ? (MI > 4 ? 1 : kQkvGI) : 4;  // row blocks whose operands are in flight together
 #pragma unroll
@@ -1258,6 +1300,7 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
           if constexpr (NIB) y = szn.x * (y - szn.y * rs_lds[ml]);
           if constexpr (CVT) y = szn.x * y;
           if constexpr (AFF) y = gemm_affine(y, adn);
+          if constexpr (LORA) y = gemm_lora(p, y, m < M ? m : 0, lc);
           gemm_store_elem<EP>(p, y, m, n, m < M, row, Cd, opv[i][r], qg[i][r], qc);
         }
       }
@@ -1266,9 +1309,9 @@ __global__ __launch_bounds__(512, 1) void gemm_glds_kernel(GemmParams p) {
   }
 }
 
-template <int WF, int EP, int BN, bool AFF = false>
+template <int WF, int EP, int BN, bool AFF = false, bool LORA = false>
 static int gemm_glds_launch(const GemmParams& p, hipStream_t s) {
-  auto kern = gemm_glds_kernel<WF, EP, BN, AFF>;
+  auto kern = gemm_glds_kernel<WF, EP, BN, AFF, LORA>;
   static bool attr_set = false;  // per instantiation, before any graph capture
   const size_t lds = GldsGeo<WF, BN>::LDS;
   if (!attr_set) {
@@ -1294,7 +1337,7 @@ static bool glds_enabled(int wf) {
 
 // 256 x 256 or 256 x 128 tiles: the shape with the fewer tile-time units over the CUs (waves of
 // tiles rounded up, a 256 x 128 tile costing kGldsCost128 % of a 256 x 256 one)
-template <int WF, int EP, bool AFF = false>
+template <int WF, int EP, bool AFF = false, bool LORA = false>
 static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   int cus = 256;
   {
@@ -1312,8 +1355,8 @@ static int gemm_glds_run(const GemmParams& p, hipStream_t s) {
   const long w128 = (mt * (p.N / 128) + cus - 1) / cus;
   const int oc = opt(LLJ_OPT_GLDS_COST128);  // A/B and tests: 0 forces 256 x 128, >= 100 prefers 256 x 256
   const long cost = oc >= 0 ? oc : kGldsCost128;
-  if (w256 > 0 && 100 * w256 <= cost * w128) return gemm_glds_launch<WF, EP, 256, AFF>(p, s);
-  return gemm_glds_launch<WF, EP, 128, AFF>(p, s);
+  if (w256 > 0 && 100 * w256 <= cost * w128) return gemm_glds_launch<WF, EP, 256, AFF, LORA>(p, s);
+  return gemm_glds_launch<WF, EP, 128, AFF, LORA>(p, s);
 }
 
 // split-K residual GEMM (few row tiles: a prompt of 256..1024 rows leaves the 4096-column GEMMs at
@@ -1371,7 +1414,7 @@ static int splitk_plan(int wfmt, int M, int N, int K, int* kcs_out) {
   return ns < 2 ? 0 : ns;
 }
 
-template <int EP, bool AFF = false>
+template <int EP, bool AFF = false, bool LORA = false>
 static int gemm_run(int wfmt, GemmParams& p, void* stream) {
   const bool zint = (wfmt & LLJ_WF_ZINT) != 0;  // int4 only: every zero is an integer
   wfmt &= ~LLJ_WF_ZINT;
@@ -1384,22 +1427,22 @@ static int gemm_run(int wfmt, GemmParams& p, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (wfmt == GWF_W4) {
     if (!p.sz) return LLJ_EINVAL;
-    if (zint && p.M >= 256 && w4z_enabled()) return gemm_glds_launch<GWF_W4Z, EP, 128, AFF>(p, s);
-    if (p.M >= 256 && p.K % 128 == 0 && glds_enabled(GWF_W4)) return gemm_glds_run<GWF_W4, EP, AFF>(p, s);
-    if (p.M >= 256) return gemm_launch<GWF_W4, EP, 256, AFF>(p, s);
-    return gemm_launch<GWF_W4, EP, kGBM, AFF>(p, s);
+    if (zint && p.M >= 256 && w4z_enabled()) return gemm_glds_launch<GWF_W4Z, EP, 128, AFF, LORA>(p, s);
+    if (p.M >= 256 && p.K % 128 == 0 && glds_enabled(GWF_W4)) return gemm_glds_run<GWF_W4, EP, AFF, LORA>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_W4, EP, 256, AFF, LORA>(p, s);
+    return gemm_launch<GWF_W4, EP, kGBM, AFF, LORA>(p, s);
   }
-  if (wfmt == GWF_W8) return p.sz ? gemm_launch<GWF_W8, EP, kGBM, AFF>(p, s) : LLJ_EINVAL;
+  if (wfmt == GWF_W8) return p.sz ? gemm_launch<GWF_W8, EP, kGBM, AFF, LORA>(p, s) : LLJ_EINVAL;
   if ((wfmt & 0xff) == GWF_W4G) {  // grouped int4: group size (128-deep chunks) in the bits above
     p.gch = wfmt >> 8;
-    return (p.sz && p.gch >= 1 && p.K % 128 == 0) ? gemm_launch<GWF_W4G, EP, kGBM, AFF>(p, s) : LLJ_EINVAL;
+    return (p.sz && p.gch >= 1 && p.K % 128 == 0) ? gemm_launch<GWF_W4G, EP, kGBM, AFF, LORA>(p, s) : LLJ_EINVAL;
   }
   if (wfmt == GWF_BF16) {
-    if (p.M >= 256 && glds_enabled(GWF_BF16)) return gemm_glds_run<GWF_BF16, EP, AFF>(p, s);
-    if (p.M >= 256) return gemm_launch<GWF_BF16, EP, 256, AFF>(p, s);
-    return gemm_launch<GWF_BF16, EP, kGBM, AFF>(p, s);
+    if (p.M >= 256 && glds_enabled(GWF_BF16)) return gemm_glds_run<GWF_BF16, EP, AFF, LORA>(p, s);
+    if (p.M >= 256) return gemm_launch<GWF_BF16, EP, 256, AFF, LORA>(p, s);
+    return gemm_launch<GWF_BF16, EP, kGBM, AFF, LORA>(p, s);
   }
-  if constexpr (!AFF) if (wfmt == GWF_I8) {
+  if constexpr (!AFF && !LORA) if (wfmt == GWF_I8) {
     if (!p.sz || !p.i8ws || p.K % 128) return LLJ_EINVAL;
     if (!p.ao16 != !p.w16 || (p.ao16 && (p.kpad < 64 || p.kpad % 64))) return LLJ_EINVAL;
     if (p.M >= 256) return gemm_launch<GWF_I8, EP, 256>(p, s);
@@ -1663,6 +1706,27 @@ int llj_gemm_qkv_rope_v2(int wfmt, const void* x, const void* W, const void* sz,
   p.ad_s = (const bf16_t*)adapter_scale; p.ad_b = (const bf16_t*)adapter_bias;
   if (p.head_size & 1 || C % 16) return LLJ_EINVAL;
   return gemm_run<GEP_QKV, true>(wfmt, p, stream);
+}
+
+// ---- LoRA (reference lora.py:310-323): llj_gemm_qkv_rope with the unmerged low-rank term of c_attn added
+// in the tile epilogue before RoPE and the KV write (register-staged and LDS-DMA kernels, the LDS-staged
+// QKV epilogue included). No LoRA operands = the op above; wfmt 0 (with and without LLJ_WF_ZINT), 1, 3 and
+// grouped int4.
+int llj_gemm_qkv_rope_lora(int wfmt, const void* x, const void* W, const void* sz, void* q_out, void* kcache,
+                           void* vcache, const float* rope, const int* pos, int B, int T, int C, int n_head, int S,
+                           void* stream, const void* lora_t, int ldt, const void* lora_B, int r, int enable_mask,
+                           float scaling) {
+  const int st = lora_args_state(lora_t, ldt, lora_B, r, enable_mask);
+  if (st == 0) return llj_gemm_qkv_rope(wfmt, x, W, sz, q_out, kcache, vcache, rope, pos, B, T, C, n_head, S, stream);
+  if (st < 0 || (wfmt & 0xff) == GWF_I8) return LLJ_EINVAL;
+  if (B < 1 || T < 1 || n_head < 1 || C % n_head || S < 1 || !pos || !rope) return LLJ_EINVAL;
+  GemmParams p{};
+  p.A = (const bf16_t*)x; p.lda = C; p.M = B * T; p.N = 3 * C; p.K = C; p.W = W; p.sz = (const float2*)sz;
+  p.q_out = (bf16_t*)q_out; p.kcache = (bf16_t*)kcache; p.vcache = (bf16_t*)vcache; p.rope = rope; p.pos = pos;
+  p.n_head = n_head; p.head_size = C / n_head; p.S = S; p.T = T;
+  p.lora = LoraArgs{lora_t, ldt, lora_B, r, enable_mask, scaling};
+  if (p.head_size & 1 || C % 16) return LLJ_EINVAL;
+  return gemm_run<GEP_QKV, false, true>(wfmt, p, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // C-ABI entry points of the weight-streaming GEMV family (device code: gemv_impl.h; the
 // per-format instantiations: gemv_w4.hip, gemv_bf16.hip, gemv_w8.hip, gemv_i8.hip, gemv_w4g.hip; their
-// adapter v2 forms: gemv_aff_*.hip).
+// adapter v2 forms: gemv_aff_*.hip; the LoRA forms of the QKV op: gemv_lora_*.hip).
 #include "gemv_impl.h"
 
 namespace llj {
@@ -10,6 +10,16 @@ int g_stream_a = 1;
 
 template <int EP>
 static int dispatch(int wf, int am, const GemvParams& p, hipStream_t s) {
+  if (p.lora.t) {  // LoRA: the LORA instantiations of the QKV op
+    if (EP != EP_QKV || p.ad_s) return LLJ_EINVAL;
+    switch (wf) {
+      case WF_W4: return gemv_launch_lora_w4(am, p, s);
+      case WF_BF16: return gemv_launch_lora_bf16(am, p, s);
+      case WF_W8: return gemv_launch_lora_w8(am, p, s);
+      case WF_W4G: return gemv_launch_lora_w4g(am, p, s);
+    }
+    return LLJ_EINVAL;  // (no LLM.int8 form)
+  }
   if (p.ad_s) {  // adapter v2: the AFF instantiations
     switch (wf) {
       case WF_W4: return gemv_launch_aff_w4(am, EP, p, s);
@@ -220,6 +230,34 @@ int llj_norm_qkv_rope_v2(int wfmt, const void* x, const void* norm_w, float eps,
   p.S = S; p.T = T; p.i8ws = i8ws;
   if (p.head_size < 2 || (p.head_size & (p.head_size - 1)) || rows > 8) return LLJ_EINVAL;  // power of two
   set_affine(p, adapter_scale, adapter_bias);
+  return run<EP_QKV>(wfmt, p, stream);
+}
+
+// ---- LoRA (reference lora.py:310-323): llj_norm_qkv_rope with the unmerged low-rank term of c_attn added
+// to the Linear's rounded output before RoPE and the KV write. No LoRA operands = the op above.
+int llj_norm_qkv_rope_lora(int wfmt, const void* x, const void* norm_w, float eps, const void* W, const void* sz,
+                           void* q_out, void* kcache, void* vcache, const float* rope, const int* pos, int B, int T,
+                           int C, int n_head, int S, int row0, int rows, const void* i8ws, const float* rowsum,
+                           const float* nstat, int npart, void* stream, const void* lora_t, int ldt,
+                           const void* lora_B, int r, int enable_mask, float scaling) {
+  const int st = lora_args_state(lora_t, ldt, lora_B, r, enable_mask);
+  if (st == 0)
+    return llj_norm_qkv_rope(wfmt, x, norm_w, eps, W, sz, q_out, kcache, vcache, rope, pos, B, T, C, n_head, S, row0,
+                             rows, i8ws, rowsum, nstat, npart, stream);
+  if (st < 0 || (wfmt & 0xff) == WF_I8) return LLJ_EINVAL;
+  // (the rank-8 form reads lora_B's rows as 16-byte words)
+  if (r == 8 && (reinterpret_cast<uintptr_t>(lora_B) & 15)) return LLJ_EINVAL;
+  GemvParams p{};
+  p.rowsum = rowsum ? rowsum + row0 : nullptr;
+  p.nstat = nstat ? nstat + row0 : nullptr; p.npart = npart;
+  if (row0 < 0 || rows < 1 || row0 + rows > B * T || n_head < 1 || C % n_head || S < 1) return LLJ_EINVAL;
+  p.A = (const bf16_t*)x + (size_t)row0 * C; p.lda = C; p.norm_w = (const bf16_t*)norm_w; p.eps = eps;
+  p.M = rows; p.m0 = row0; p.N = 3 * C; p.K = C;
+  p.W = W; p.sz = (const float2*)sz; p.q_out = (bf16_t*)q_out; p.kcache = (bf16_t*)kcache;
+  p.vcache = (bf16_t*)vcache; p.rope = rope; p.pos = pos; p.n_head = n_head; p.head_size = C / n_head;
+  p.S = S; p.T = T; p.i8ws = i8ws;
+  if (p.head_size < 2 || (p.head_size & (p.head_size - 1)) || rows > 8) return LLJ_EINVAL;  // power of two
+  p.lora = LoraArgs{(const bf16_t*)lora_t + (size_t)row0 * ldt, ldt, lora_B, r, enable_mask, scaling};
   return run<EP_QKV>(wfmt, p, stream);
 }
 

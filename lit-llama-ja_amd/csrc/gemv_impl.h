@@ -131,6 +131,9 @@ struct GemvParams {
   const bf16_t* ad_b;
   const bf16_t* ad_s2;
   const bf16_t* ad_b2;
+  // LoRA (LORA instantiations only, EP_QKV; reference lora.py:310-323): the unmerged c_attn's low-rank
+  // term; lora.t = the down-projection of this call's rows (local row m at m * ldt), bf16
+  LoraArgs lora;
 };
 constexpr int kNstRows = 16;
 
@@ -469,10 +472,12 @@ __host__ __device__ constexpr int tail_floats(int nw) { return 8 + 24 * nw; }
 // once per workgroup instead of once per tile. TPW > 1 only for the standalone LDS-A forms.
 // AFF: the Linear's output passes through the adapter v2 affine (GemvParams ad_s / ad_b) before the
 // epilogue consumes it -- a compile-time property, so the AFF = false instantiations carry nothing of it.
-template <int WF, int AM, int EP, int NW, int D, int MB, int TPW = 1, bool AFF = false>
+// LORA (EP_QKV): the unmerged LoRA term is added to the Linear's rounded output at the same point.
+template <int WF, int AM, int EP, int NW, int D, int MB, int TPW = 1, bool AFF = false, bool LORA = false>
 __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, unsigned char* smem) {
   static_assert(TPW == 1 || (WF != WF_I8 && AM != AM_GLOBAL), "multi-tile: LDS-A forms");
   static_assert(!AFF || WF != WF_I8, "adapter v2 affine: not on the LLM.int8 forms");
+  static_assert(!LORA || (EP == EP_QKV && WF != WF_I8 && !AFF), "LoRA: the c_attn forms, not LLM.int8, not with adapter v2");
   constexpr int TL_RS = 8 + 16 * NW;
   constexpr bool DUAL = (EP == EP_SWIGLU);
   constexpr bool I8 = (WF == WF_I8);
@@ -918,10 +923,35 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   float e_rs[4] = {0.f, 0.f, 0.f, 0.f};  // caller's row sums (p.rowsum) of rows 4*grp + r
   // AFF: adapter_scale / adapter_bias of this lane's column in every tile slot (raw bf16; [1]: c_fc2's)
   bf16_t e_as[AFF ? TPW : 1][2], e_ab[AFF ? TPW : 1][2];
+  // LORA, one tile per workgroup: lora_B's row of this lane's column at rank 8 (8 bf16, one 16-byte load; row 0
+  // of the matrix for a column of a disabled group -- loaded, not used). Other ranks, and the multi-tile forms
+  // (whose 4 words per tile slot held across the stream spilled to scratch), read theirs in the epilogue,
+  // in one batch with t.
+  constexpr bool LPRE = LORA && TPW == 1;
+  uint32_t e_lb[4] = {0u, 0u, 0u, 0u};
+  auto lora_brow = [&](const int n0, const int n, int& gi, bool& en) -> size_t {  // (en ? row of lora_B : 0)
+    const int Cd = p.n_head * p.head_size;
+    const int region = n0 >= 2 * Cd ? 2 : (n0 >= Cd ? 1 : 0);  // a 16-column tile lies in one of q, k, v
+    en = (p.lora.mask >> region) & 1;
+    gi = en ? lora_slab(p.lora.mask, region) : 0;  // the group's slab of lora_A / lora_B (0: a valid one)
+    return en ? (size_t)gi * Cd + (n - region * Cd) : 0;
+  };
   auto issue_const = [&]() {  // weights-side epilogue operands (never written in a launch)
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
       const int n = nj[j];
+      if constexpr (LPRE) {
+        int gi;
+        bool en;
+        const size_t br = lora_brow(ntj[j] * 16, n, gi, en);
+        if (p.lora.r == 8) {  // uniform
+          const uint4 bv = reinterpret_cast<const uint4*>(p.lora.B)[br];
+          e_lb[0] = bv.x;
+          e_lb[1] = bv.y;
+          e_lb[2] = bv.z;
+          e_lb[3] = bv.w;
+        }
+      }
       if constexpr (AFF) {  // nj is a real column in every slot (clamped tile): branch-free
         e_as[j][0] = p.ad_s[n];
         e_ab[j][0] = p.ad_b[n];
@@ -1488,6 +1518,37 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
       y = round_bf(round_bf(round_bf(y) + bf2f(ab)) * bf2f(as));
       if (DUAL) y2 = round_bf(round_bf(round_bf(y2) + bf2f(ab2)) * bf2f(as2));
     }
+    if constexpr (LORA) {
+      // unmerged LoRA (lora.py:310-323 on bf16 tensors): d = bf16(t[m] . B[n']), y = bf16(bf16(y) +
+      // bf16(d * scaling)) on the columns of enabled groups. Branch-free: clamped addresses (row 0 of t for
+      // an inactive element, row 0 of B for a disabled column), the result selected.
+      int gi;
+      bool en;
+      const size_t br = lora_brow(n0, n, gi, en);
+      const int rk = p.lora.r;
+      const bf16_t* tr = reinterpret_cast<const bf16_t*>(p.lora.t) + (size_t)(act ? m : 0) * p.lora.ldt + gi * rk;
+      float d = 0.f;
+      if (LPRE && rk == 8) {  // uniform: lora_B's row came in with the epilogue constants
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          d = fmaf(bf2f(tr[2 * i]), bflo(e_lb[i]), d);
+          d = fmaf(bf2f(tr[2 * i + 1]), bfhi(e_lb[i]), d);
+        }
+      } else if (rk == 8) {  // uniform
+        const uint4 bv = reinterpret_cast<const uint4*>(p.lora.B)[br];
+        const uint32_t bw[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          d = fmaf(bf2f(tr[2 * i]), bflo(bw[i]), d);
+          d = fmaf(bf2f(tr[2 * i + 1]), bfhi(bw[i]), d);
+        }
+      } else {
+        const bf16_t* bp = reinterpret_cast<const bf16_t*>(p.lora.B) + br * rk;
+        for (int i = 0; i < rk; ++i) d = fmaf(bf2f(tr[i]), bf2f(bp[i]), d);
+      }
+      const float yl = round_bf(round_bf(y) + round_bf(round_bf(d) * p.lora.scaling));
+      y = en ? yl : y;
+    }
     bool big = false;
     if (EP == EP_QKV) {
       // c_attn output rounded to bf16 (model.py:204), then RoPE in fp32 (model.py:318-329)
@@ -1630,10 +1691,10 @@ __device__ __forceinline__ void gemv_body(const GemvParams& p, const int nt0, un
   LLJ_STAMP(5);
 }
 
-template <int WF, int AM, int EP, int NW, int D, int MB, int TPW, bool AFF = false>
+template <int WF, int AM, int EP, int NW, int D, int MB, int TPW, bool AFF = false, bool LORA = false>
 __global__ __launch_bounds__(NW * 64) void gemv_kernel(GemvParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  gemv_body<WF, AM, EP, NW, D, MB, TPW, AFF>(p, blockIdx.x * TPW, smem);
+  gemv_body<WF, AM, EP, NW, D, MB, TPW, AFF, LORA>(p, blockIdx.x * TPW, smem);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1765,10 +1826,10 @@ constexpr int d_of() {
 #ifndef LLJ_DI8Q
 #define LLJ_DI8Q 4  // AM_I8Q: chunks (2 KiB of int8 weights each) in flight per wave (8 spills)
 #endif
-template <int WF, int AM, int EP, int MB, int NW, int TPW, bool AFF = false>
+template <int WF, int AM, int EP, int MB, int NW, int TPW, bool AFF = false, bool LORA = false>
 static int launch_t(const GemvParams& p, hipStream_t s) {
   const size_t sm = gemv_smem(WF, AM, p.M, p.K, NW, TPW);
-  auto kern = gemv_kernel<WF, AM, EP, NW, AM == AM_I8Q ? (EP == EP_SWIGLU ? LLJ_DMS : LLJ_DI8Q) : d_of<EP, MB>(), MB, TPW, AFF>;
+  auto kern = gemv_kernel<WF, AM, EP, NW, AM == AM_I8Q ? (EP == EP_SWIGLU ? LLJ_DMS : LLJ_DI8Q) : d_of<EP, MB>(), MB, TPW, AFF, LORA>;
   static bool attr_set[16] = {};  // per instantiation and device; set before any graph capture
   if (sm > 64 * 1024) {
     int dev = 0;
@@ -1785,29 +1846,29 @@ static int launch_t(const GemvParams& p, hipStream_t s) {
   return 0;
 }
 
-template <int WF, int AM, int EP, int MB, int NW = nw_of<AM>(), bool AFF = false>
+template <int WF, int AM, int EP, int MB, int NW = nw_of<AM>(), bool AFF = false, bool LORA = false>
 static int launch_mb(const GemvParams& p, hipStream_t s) {
   if constexpr (tpw_ok<WF, AM>() && MB > 1) {  // M == 1 (MB 1) always one tile: pick_tpw
     // the residual ops (8 chunks in flight) take at most 2 tiles per workgroup (3 and 4 spill;
     // C / 16 tiles need 2 only past 256 CUs' worth: 13B / 30B / 65B)
     const int t = pick_tpw(p.N / 16, p.M);
     switch (EP == EP_RESID && t > 2 ? 2 : t) {
-      case 2: return launch_t<WF, AM, EP, MB, NW, 2, AFF>(p, s);
-      case 3: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 3, AFF>(p, s); break;
-      case 4: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 4, AFF>(p, s); break;
+      case 2: return launch_t<WF, AM, EP, MB, NW, 2, AFF, LORA>(p, s);
+      case 3: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 3, AFF, LORA>(p, s); break;
+      case 4: if constexpr (EP != EP_RESID) return launch_t<WF, AM, EP, MB, NW, 4, AFF, LORA>(p, s); break;
       default: break;
     }
   }
-  return launch_t<WF, AM, EP, MB, NW, 1, AFF>(p, s);
+  return launch_t<WF, AM, EP, MB, NW, 1, AFF, LORA>(p, s);
 }
 
-template <int WF, int AM, int EP, bool AFF = false>
+template <int WF, int AM, int EP, bool AFF = false, bool LORA = false>
 static int launch(const GemvParams& p, hipStream_t s) {
   if constexpr (am_stream(AM) || AM == AM_I8Q || AM == AM_I8S) {  // batched rows only (M <= 8)
     if constexpr (EP == EP_RESID && LLJ_NWR != kNW)
       if (p.K >= LLJ_NWR_KMIN) return launch_mb<WF, AM, EP, 8, LLJ_NWR, AFF>(p, s);
     if constexpr (EP == EP_SWIGLU && LLJ_NWS != LLJ_NWM) return launch_mb<WF, AM, EP, 8, LLJ_NWS, AFF>(p, s);
-    return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF>(p, s);
+    return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF, LORA>(p, s);
   } else {
   // the register-staged prologue has an M == 1 class (bs = 1 decode) and an M <= 8 class
   if constexpr (EP == EP_RESID && AM != AM_GLOBAL && LLJ_NWR != kNW) {
@@ -1818,9 +1879,9 @@ static int launch(const GemvParams& p, hipStream_t s) {
       return launch_t<WF, AM, EP, 8, LLJ_NWR, 1, AFF>(p, s);
     }
   }
-  if (WF != WF_I8 && AM != AM_GLOBAL && p.M == 1) return launch_mb<WF, AM, EP, 1, nw_of<AM>(), AFF>(p, s);
-  if constexpr (AM != AM_GLOBAL && WF != WF_I8) return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF>(p, s);
-  return launch_mb<WF, AM, EP, 8, nw_of<AM>(), AFF>(p, s);
+  if (WF != WF_I8 && AM != AM_GLOBAL && p.M == 1) return launch_mb<WF, AM, EP, 1, nw_of<AM>(), AFF, LORA>(p, s);
+  if constexpr (AM != AM_GLOBAL && WF != WF_I8) return launch_mb<WF, AM, EP, 8, LLJ_NWM, AFF, LORA>(p, s);
+  return launch_mb<WF, AM, EP, 8, nw_of<AM>(), AFF, LORA>(p, s);
   }
 }
 
@@ -1864,6 +1925,11 @@ int gemv_launch_aff_w4(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_aff_bf16(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_aff_w8(int am, int ep, const GemvParams& p, hipStream_t s);
 int gemv_launch_aff_w4g(int am, int ep, const GemvParams& p, hipStream_t s);
+// ... and the LoRA (LORA) instantiations of EP_QKV (gemv_lora_*.hip; no LLM.int8 form)
+int gemv_launch_lora_w4(int am, const GemvParams& p, hipStream_t s);
+int gemv_launch_lora_bf16(int am, const GemvParams& p, hipStream_t s);
+int gemv_launch_lora_w8(int am, const GemvParams& p, hipStream_t s);
+int gemv_launch_lora_w4g(int am, const GemvParams& p, hipStream_t s);
 
 template <int WF, int AM, bool AFF = false>
 static int launch_ep(int ep, const GemvParams& p, hipStream_t s) {
@@ -1894,6 +1960,17 @@ static int launch_fmt(int am, int ep, const GemvParams& p, hipStream_t s) {
     if (am == AM_LDS) return launch_ep<WF, AM_LDS, AFF>(ep, p, s);
     return launch_ep<WF, AM_GLOBAL, AFF>(ep, p, s);
   }
+}
+// EP_QKV with the LoRA term (llj_norm_qkv_rope_lora)
+template <int WF>
+static int launch_lora_fmt(int am, const GemvParams& p, hipStream_t s) {
+  static_assert(WF != WF_I8, "LoRA: no LLM.int8 form");
+  if (am == AM_SNORM) return launch<WF, AM_SNORM, EP_QKV, false, true>(p, s);
+  if (am == AM_STREAM) return launch<WF, AM_STREAM, EP_QKV, false, true>(p, s);
+  if (am == AM_NORM) return launch<WF, AM_NORM, EP_QKV, false, true>(p, s);
+  if (am == AM_LDS) return launch<WF, AM_LDS, EP_QKV, false, true>(p, s);
+  if (am == AM_GLOBAL) return launch<WF, AM_GLOBAL, EP_QKV, false, true>(p, s);
+  return LLJ_EINVAL;
 }
 
 }  // namespace llj

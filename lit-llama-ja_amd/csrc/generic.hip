@@ -68,15 +68,16 @@ __global__ __launch_bounds__(256) void g_rmsnorm_kernel(const T* __restrict__ x,
 // (q - zero) * scale in fp32 (quantization.py:250-267, 390-409). One wave per output column, lanes
 // over k, up to 8 rows per wave. T: activation (and dense weight) type. AFF (adapter v2, reference
 // adapter_v2.py:28-31): the Linear's output through ad_s[n] * (y + ad_b[n]) before the residual add,
-// every step rounded on the bf16 path, evaluated as written in fp32.
+// every step rounded on the bf16 path, evaluated as written in fp32. LORA (reference lora.py:310-323, the
+// unmerged c_attn; N % 3 == 0): columns of an enabled group get rnd(y + rnd(rnd(t[m] . B[n']) * scaling)).
 constexpr int GL_ROWS = 8;
-template <int WK, typename T, bool AFF = false>
+template <int WK, typename T, bool AFF = false, bool LORA = false>
 __global__ __launch_bounds__(256) void g_linear_kernel(const T* __restrict__ x, int ldx, int M, int K,
                                                        const void* __restrict__ W, const float* __restrict__ sc,
                                                        const float* __restrict__ zr, int bits, int group, int N,
                                                        T* __restrict__ y, int ldy, const T* resid, int ldr,
                                                        const T* __restrict__ ad_s = nullptr,
-                                                       const T* __restrict__ ad_b = nullptr) {
+                                                       const T* __restrict__ ad_b = nullptr, LoraArgs lo = {}) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -113,6 +114,19 @@ __global__ __launch_bounds__(256) void g_linear_kernel(const T* __restrict__ x, 
         // fp32: the product is pinned (empty asm) so that it is not contracted with the residual add
         // into one fma -- the expression is evaluated as written, each operation rounded
         asm volatile("" : "+v"(v));
+      }
+      if constexpr (LORA) {
+        const int Ng = N / 3, g = n / Ng;
+        if ((lo.mask >> g) & 1) {
+          const int gi = lora_slab(lo.mask, g);
+          const T* tr = reinterpret_cast<const T*>(lo.t) + m * lo.ldt + (size_t)gi * lo.r;
+          const T* br = reinterpret_cast<const T*>(lo.B) + ((size_t)gi * Ng + (n - g * Ng)) * lo.r;
+          float d = 0.f;
+          for (int j = 0; j < lo.r; ++j) d += ldv(tr, j) * ldv(br, j);
+          float pr = rnd<T>(d) * lo.scaling;
+          asm volatile("" : "+v"(pr));  // (fp32: the product is not contracted into the sum)
+          v = rnd<T>(v + rnd<T>(pr));
+        }
       }
       if (resid) v = ldv(resid, m * ldr + n) + v;
       stv(y, m * ldy + n, v);
@@ -389,6 +403,31 @@ int llj_g_linear_v2(int wkind, const void* x, int ldx, int M, int K, const void*
   hipLaunchKernelGGL((g_linear_kernel<WK, T, true>), grid, dim3(256), 0, s, (const T*)x, ldx, M, K, W, scales, zeros, \
                      WK == 1 ? 16 : bits, WK == 1 ? K : group, N, (T*)y, ldy, (const T*)resid, ldr,                  \
                      (const T*)adapter_scale, (const T*)adapter_bias)
+  if (wkind == 1) LLJ_DT(dt, LLJ_GL(1, bf16_t), LLJ_GL(1, float));
+  else LLJ_DT(dt, LLJ_GL(0, bf16_t), LLJ_GL(0, float));
+#undef LLJ_GL
+  LLJ_CHECK_LAUNCH();
+  return 0;
+}
+
+int llj_g_linear_lora(int wkind, const void* x, int ldx, int M, int K, const void* W, const float* scales,
+                      const float* zeros, int bits, int group, int N, void* y, int ldy, const void* resid, int ldr,
+                      int dt, void* stream, const void* lora_t, int ldt, const void* lora_B, int r, int enable_mask,
+                      float scaling) {
+  const int st = lora_args_state(lora_t, ldt, lora_B, r, enable_mask);
+  if (st == 0)
+    return llj_g_linear(wkind, x, ldx, M, K, W, scales, zeros, bits, group, N, y, ldy, resid, ldr, dt, stream);
+  LLJ_REQUIRE(st == 1 && N % 3 == 0 && !resid);
+  LLJ_REQUIRE(x && W && y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N && (dt == 0 || dt == 1));
+  LLJ_REQUIRE(wkind == 1 || (wkind == 0 && scales && zeros && (bits == 2 || bits == 4 || bits == 8) && group > 0 &&
+                             K % (8 / bits) == 0));
+  const dim3 grid((N + 3) / 4, (M + GL_ROWS - 1) / GL_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  const LoraArgs lo{lora_t, ldt, lora_B, r, enable_mask, scaling};
+#define LLJ_GL(WK, T) \
+  hipLaunchKernelGGL((g_linear_kernel<WK, T, false, true>), grid, dim3(256), 0, s, (const T*)x, ldx, M, K, W, scales, \
+                     zeros, WK == 1 ? 16 : bits, WK == 1 ? K : group, N, (T*)y, ldy, (const T*)nullptr, 0,            \
+                     (const T*)nullptr, (const T*)nullptr, lo)
   if (wkind == 1) LLJ_DT(dt, LLJ_GL(1, bf16_t), LLJ_GL(1, float));
   else LLJ_DT(dt, LLJ_GL(0, bf16_t), LLJ_GL(0, float));
 #undef LLJ_GL

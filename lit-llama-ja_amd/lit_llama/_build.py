@@ -12,7 +12,7 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 CSRC = PKG.parent / "csrc"
-INCLUDE = PKG.parent.parent / "include"  # the public C ABI header (llj_layer)
+INCLUDE = PKG.parent.parent / "include"  # the public C ABI headers (lit_llama_amd.h and what it includes)
 OUT = PKG / "_lljamd.so"
 ARCH = os.environ.get("LLJ_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-function",
@@ -32,7 +32,7 @@ def needs_build() -> bool:
     if not OUT.exists():
         return True
     t = OUT.stat().st_mtime
-    return any(p.stat().st_mtime > t for p in list(CSRC.glob("*")) + [INCLUDE / "lit_llama_amd.h"])
+    return any(p.stat().st_mtime > t for p in list(CSRC.glob("*")) + list(INCLUDE.glob("*.h")))
 
 
 OBJ_CACHE = PKG.parent.parent / "build" / "obj"  # per-source objects of the in-tree library (git-ignored)
@@ -42,7 +42,7 @@ def _stale(obj: Path, src: Path) -> bool:
     if not obj.exists():
         return True
     t = obj.stat().st_mtime
-    deps = [src] + list(CSRC.glob("*.h")) + [INCLUDE / "lit_llama_amd.h", Path(__file__)]
+    deps = [src] + list(CSRC.glob("*.h")) + list(INCLUDE.glob("*.h")) + [Path(__file__)]
     return any(d.stat().st_mtime > t for d in deps)
 
 

@@ -1,4 +1,5 @@
-"""ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h).
+"""ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h and the
+lit_llama_amd_lora.h it includes).
 
 The library is the only compute path of this package: there is no CPU or eager-PyTorch
 fallback. If it is missing or the device is not a ROCm GPU, calls raise.
@@ -99,6 +100,17 @@ SIGNATURES = {
     "llj_g_linear_v2": [_I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
 }
 
+# the LoRA entry points (include/lit_llama_amd_lora.h, which lit_llama_amd.h includes): the merge, and the op
+# of the same name + (lora_t, ldt, lora_B, r, enable_mask, scaling). A table of its own, as the header is.
+LORA_SIGNATURES = {
+    "llj_lora_merge": [_P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
+    "llj_norm_qkv_rope_lora": [_I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
+                               _I, _P, _P, _I, _P, _I, _I, _F],
+    "llj_gemm_qkv_rope_lora": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _F],
+    "llj_g_linear_lora": [_I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _I,
+                          _F],
+}
+
 _lib = None
 
 
@@ -121,7 +133,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no fallback path.")
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, argt in SIGNATURES.items():
+        for name, argt in {**SIGNATURES, **LORA_SIGNATURES}.items():
             f = getattr(L, name)
             f.argtypes = argt
             f.restype = ctypes.c_int

@@ -95,10 +95,11 @@ class DecodeSession:
         # decode-step operands (fixed for the session)
         self.specs = m._layer_specs()
         if m._generic():  # the any-shape kernels (csrc/generic.hip)
-            self.work = _Work(m.config, B, self.dev, False, self.S, generic=True, dtype=m.act_dtype())
+            self.work = _Work(m.config, B, self.dev, False, self.S, generic=True, dtype=m.act_dtype(),
+                              lora_cols=self.specs.get("lora_cols", 0))
         else:
             need_i8 = any(s[0] == 2 for layer in self.specs["layers"] for s in layer) or self.specs["head"][0] == 2
-            self.work = _Work(m.config, B, self.dev, need_i8, self.S)
+            self.work = _Work(m.config, B, self.dev, need_i8, self.S, lora_cols=self.specs.get("lora_cols", 0))
             m._enable_i8_handoff(self.work, self.specs)
         self.graph = None  # the caches / operands may have changed
 

@@ -273,6 +273,39 @@ def _lcall(name: str, af, *args) -> None:
 _NO_AFFINE = (None,) * 5
 
 
+def _lora(lin: nn.Module, dtype=None):
+    """The unmerged LoRA operands of c_attn (lit_llama.lora.lora_operands; reference lora.py:310-323), or
+    None: a Linear without LoRA, or a merged one -- its weight holds the update and it runs as the base
+    Linear. Unsupported combinations raise here, before any launch."""
+    prm = lin.__dict__.get("_parameters") or {}
+    if prm.get("lora_A") is None:
+        return None
+    from .lora import lora_operands
+
+    return lora_operands(lin, dtype)
+
+
+def _lora_specs(attns, dtype) -> dict:
+    """{"lora": per-layer operands or None, "lora_cols": the widest down-projection} -- empty for a model
+    with no unmerged LoRA Linear, which then issues exactly the base model's calls."""
+    ops = [_lora(a.c_attn, dtype) for a in attns]
+    if all(o is None for o in ops):
+        return {}
+    return {"lora": ops, "lora_cols": max(o["cols"] for o in ops if o is not None)}
+
+
+def _lora_image(lo) -> torch.Tensor:
+    """lora_A as the streaming kernels read it (lit_llama.lora.lora_a_image: bf16, zero-padded rows)."""
+    from .lora import lora_a_image
+
+    return lora_a_image(lo["lin"])
+
+
+def _lora_tail(lo, t: torch.Tensor) -> tuple:
+    """(lora_t, ldt, lora_B, r, enable_mask, scaling): the arguments a `*_lora` entry point adds."""
+    return t.data_ptr(), t.stride(0), lo["B"].data_ptr(), lo["r"], lo["mask"], lo["scaling"]
+
+
 def _enable_i8_handoff(w: "_Work", specs) -> None:
     """The LLM.int8 statistics hand-off (see _Work) when every Linear of every layer is LLM.int8."""
     w.i8s = w.y_st is not None and all(s[0] == 2 for layer in specs["layers"] for s in layer)
@@ -282,11 +315,17 @@ class _Work:
     """Per-call scratch for M rows (allocated from torch's caching allocator)."""
 
     def __init__(self, cfg: LLaMAConfig, M: int, device, need_i8: bool, S: int = 0, gemm: bool = False,
-                 generic: bool = False, dtype=torch.bfloat16):
+                 generic: bool = False, dtype=torch.bfloat16, lora_cols: int = 0):
         C, H = cfg.n_embd, MLP.hidden(cfg)
         bf = torch.bfloat16
         self.generic = generic  # the any-shape kernels (LLaMA._blocks_generic)
         self.dt = _dt_code(dtype)
+        # unmerged LoRA: t = rms_1(x) . lora_A^T (M, lora_cols), padded in columns to what the kernel that
+        # writes it tiles by (the prefill GEMM 128, the decode GEMV 16; the any-shape kernel none)
+        self.lt = None
+        if lora_cols:
+            ldt = lora_cols if generic else (lora_cols + 127) // 128 * 128 if gemm else (lora_cols + 15) // 16 * 16
+            self.lt = torch.empty(M, ldt, dtype=dtype if generic else bf, device=device)
         if generic:
             bf = dtype  # fp32 models run here with fp32 activations
             self.x = torch.empty(M, C, dtype=bf, device=device)
@@ -450,10 +489,10 @@ class LLaMA(nn.Module):
         dev = idx.device
         specs = self._layer_specs()
         if self._generic():
-            w = _Work(cfg, M, dev, False, S, generic=True, dtype=self.act_dtype())
+            w = _Work(cfg, M, dev, False, S, generic=True, dtype=self.act_dtype(), lora_cols=specs.get("lora_cols", 0))
         else:
             need_i8 = any(s[0] == 2 for layer in specs["layers"] for s in layer) or specs["head"][0] == 2
-            w = _Work(cfg, M, dev, need_i8, S, gemm=self._gemm_ok(specs, M))
+            w = _Work(cfg, M, dev, need_i8, S, gemm=self._gemm_ok(specs, M), lora_cols=specs.get("lora_cols", 0))
             w.flash = self._flash_ok(pos, T, S)
             self._enable_i8_handoff(w, specs)
         st = _hip.stream()
@@ -491,6 +530,8 @@ class LLaMA(nn.Module):
                                                           blk.mlp.c_fc2, blk.mlp.c_proj))
                           for blk in self.transformer.h],
                "head_affine": _affine(self.lm_head, dt)}
+        # unmerged LoRA operands of c_attn, next to the affine (nothing for a base or merged model)
+        aff.update(_lora_specs([blk.attn for blk in self.transformer.h], dt))
         if self._generic():
             return {"layers": [tuple(_gspec(m) for m in (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc1,
                                                          blk.mlp.c_fc2, blk.mlp.c_proj))
@@ -619,8 +660,18 @@ class LLaMA(nn.Module):
             else:
                 _hip.call("llj_rmsnorm_rows", w.x.data_ptr(), blk.rms_1.scale.data_ptr(), blk.rms_1.eps,
                           w.xn.data_ptr(), None, M, C, st)
-                _lcall("llj_gemm_qkv_rope", aa, _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa), w.q.data_ptr(),
-                       kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, st)
+                lo = specs["lora"][i] if "lora" in specs else None
+                if lo is not None:  # unmerged LoRA: t = xn . lora_A^T, then c_attn with the low-rank epilogue
+                    img = _lora_image(lo)
+                    _hip.call("llj_gemm_linear", 1, w.xn.data_ptr(), C, img.data_ptr(), None, w.lt.data_ptr(),
+                              w.lt.stride(0), M, w.lt.stride(0), C, st)
+                    _hip.call("llj_gemm_qkv_rope_lora", _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa),
+                              w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(),
+                              B, T, C, nh, S, st, *_lora_tail(lo, w.lt))
+                else:
+                    _lcall("llj_gemm_qkv_rope", aa, _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa),
+                           w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B,
+                           T, C, nh, S, st)
             self._attention(w, kc, vc, pos, B, T, S, st, i)
             self._gemm_resid(_gz(fp, blk.attn.c_proj), w.y, wp, sp, w.x, M, C, C, w, st, ap)
             if f1 != f2:
@@ -674,8 +725,18 @@ class LLaMA(nn.Module):
                        x.stride(0), M, N, K, st)
 
     @staticmethod
-    def _glinear(spec, A, M, K, N, out, resid, st, af=None):
+    def _glinear(spec, A, M, K, N, out, resid, st, af=None, lora=None):
+        """lora: (t, operands) of an unmerged LoRA Linear (_lora) -- llj_g_linear_lora."""
         kind, W, sc, zr, bits, group = spec
+        if lora is not None:
+            if kind == 2 or af is not None or resid is not None:
+                raise NotImplementedError("LoRA: dense or gptq Linears without adapter v2 parameters or a residual")
+            if kind == 1 and W.dtype != A.dtype:
+                raise TypeError(f"dense Linear weight {W.dtype} with {A.dtype} activations")
+            _hip.call("llj_g_linear_lora", kind, A.data_ptr(), A.stride(0), M, K, W.data_ptr(), _hip.ptr(sc), _hip.ptr(zr),
+                      bits, group, N, out.data_ptr(), out.stride(0), None, 0, _dt_code(A.dtype), st,
+                      *_lora_tail(lora[1], lora[0]))
+            return
         if kind == 2:  # LLM.int8 (Linear8bitLt._gspec): statistics + int8 / fp16 products on f16(A)
             ws = torch.empty(_hip.lib().llj_g_i8_ws_bytes(M, K), dtype=torch.uint8, device=A.device)
             _hip.call("llj_g_i8_linear", A.data_ptr(), A.stride(0), M, K, W.data_ptr(), sc.data_ptr(),
@@ -702,7 +763,12 @@ class LLaMA(nn.Module):
             kc, vc = kv[i]
             _hip.call("llj_g_rmsnorm", w.x.data_ptr(), C, blk.rms_1.scale.data_ptr(), blk.rms_1.eps, w.xn.data_ptr(), C,
                       M, C, w.dt, st)
-            self._glinear(sa, w.xn, M, C, 3 * C, w.qkv, None, st, aa)
+            lo = specs["lora"][i] if "lora" in specs else None
+            if lo is not None:  # unmerged LoRA: t = xn . lora_A^T, then c_attn with the low-rank term
+                self._glinear((1, lo["A"], None, None, 16, C), w.xn, M, C, lo["cols"], w.lt, None, st)
+                self._glinear(sa, w.xn, M, C, 3 * C, w.qkv, None, st, aa, (w.lt, lo))
+            else:
+                self._glinear(sa, w.xn, M, C, 3 * C, w.qkv, None, st, aa)
             _hip.call("llj_g_rope_kv", w.qkv.data_ptr(), w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                       self.rope_cache.data_ptr(), pos.data_ptr(), B, T, C, nh, S, w.dt, st)
             _hip.call("llj_g_attention", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(), pos.data_ptr(),
@@ -755,8 +821,20 @@ class LLaMA(nn.Module):
             else:
                 src, nw = w.x, blk.rms_1.scale.data_ptr()
             nst = w.nst if (w.hand and i > 0 and fa != 2) else None
+            lo = specs["lora"][i] if "lora" in specs else None
             for r0 in range(0, M if src is not None else 0, QKV_ROWS):
                 r = min(QKV_ROWS, M - r0)
+                if lo is not None:
+                    # unmerged LoRA: t = rms_1(x) . lora_A^T as a small dense Linear on the same rows (and the
+                    # same norm hand-off), then c_attn with the low-rank term in its epilogue
+                    ldt = w.lt.stride(0)
+                    _hip.call("llj_norm_linear", 1, src[r0].data_ptr(), nw, blk.rms_1.eps, _lora_image(lo).data_ptr(),
+                              None, w.lt[r0].data_ptr(), ldt, r, ldt, C, None, r0, None,
+                              None if nst is None else nst[r0].data_ptr(), w.npart, st)
+                    _hip.call("llj_norm_qkv_rope_lora", fa, src.data_ptr(), nw, blk.rms_1.eps, wa.data_ptr(), P(sa),
+                              w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), rope.data_ptr(), pos.data_ptr(), B, T, C,
+                              nh, S, r0, r, P(w.i8ws), P(rs), P(nst), w.npart, st, *_lora_tail(lo, w.lt))
+                    continue
                 _lcall("llj_norm_qkv_rope", aa, fa, src.data_ptr(), nw, blk.rms_1.eps, wa.data_ptr(), P(sa),
                        w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), rope.data_ptr(), pos.data_ptr(), B, T, C, nh,
                        S, r0, r, P(w.i8ws), P(rs), P(nst), w.npart, st)
@@ -919,13 +997,14 @@ class _BlockHost:
         M = B * T
         mods = (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc1, blk.mlp.c_fc2, blk.mlp.c_proj)
         aff = [tuple(_affine(m, x.dtype) for m in mods)]
+        lora = _lora_specs([blk.attn], x.dtype)
         if cfg.kernel_support() is not None or x.dtype == torch.float32:  # the any-shape kernels
-            specs = {"layers": [tuple(_gspec(m) for m in mods)], "affine": aff}
-            w = _Work(cfg, M, x.device, False, generic=True, dtype=x.dtype)
+            specs = {"layers": [tuple(_gspec(m) for m in mods)], "affine": aff, **lora}
+            w = _Work(cfg, M, x.device, False, generic=True, dtype=x.dtype, lora_cols=lora.get("lora_cols", 0))
         else:
-            specs = {"layers": [tuple(_wspec(m) for m in mods)], "affine": aff}
+            specs = {"layers": [tuple(_wspec(m) for m in mods)], "affine": aff, **lora}
             need_i8 = any(s[0] == 2 for s in specs["layers"][0])
-            w = _Work(cfg, M, x.device, need_i8)
+            w = _Work(cfg, M, x.device, need_i8, lora_cols=lora.get("lora_cols", 0))
         w.x.copy_(x.reshape(M, C))
         kv = [(torch.zeros(B, cfg.n_head, T, C // cfg.n_head, dtype=w.x.dtype, device=x.device),
                torch.zeros(B, cfg.n_head, T, C // cfg.n_head, dtype=w.x.dtype, device=x.device))]

@@ -235,6 +235,10 @@ class ColBlockQuantizedLinear(torch.nn.Module):
         if inp.dtype not in (torch.bfloat16, torch.float32):
             raise TypeError(f"ColBlockQuantizedLinear HIP path computes in bfloat16 or float32, got {inp.dtype}")
         K, N = self.in_features, self.out_features
+        if "lora_A" in self._parameters:  # LoRA (lit_llama.lora): the unmerged form beside the quantized weight
+            from .lora import lora_linear_forward
+
+            return lora_linear_forward(self, inp)
         af = None
         if "adapter_scale" in self._parameters:  # adapter v2: scale * (quantized_linear(x) + bias) in the same launch
             from .model import _affine
@@ -424,6 +428,10 @@ class Linear8bitLt(torch.nn.Module):
             from .model import _affine
 
             _affine(self)
+        if "lora_A" in self._parameters:  # LoRA on an LLM.int8 Linear: NotImplementedError
+            from .lora import lora_operands
+
+            lora_operands(self, x.dtype)
         # the any-shape LLM.int8 kernels: shapes outside the streaming tiling, and fp32 input (cast to
         # fp16 inside and the result back to fp32, as bitsandbytes' MatMul8bitLt does)
         if self.in_features % 128 or self.out_features % 16 or x.dtype == torch.float32:
