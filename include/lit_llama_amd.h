@@ -494,4 +494,7 @@ int llj_stream_read(const void* p, size_t bytes, float* out, int grid, void* str
  * are declared in a header of their own, part of this ABI. */
 #include "lit_llama_amd_lora.h"
 
+/* The scoring entry points (llj_nll, llj_g_nll: per-token negative log-likelihood over logits) likewise. */
+#include "lit_llama_amd_nll.h"
+
 #endif /* LIT_LLAMA_AMD_H */

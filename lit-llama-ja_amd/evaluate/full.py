@@ -2,7 +2,8 @@
 (main 46-140, the loop 114-129): the text is encoded with the SentencePiece Tokenizer (BOS, no
 EOS), trimmed to 256 * block_size tokens, and cut into windows of 2048 tokens; every window is one
 no-cache LLaMA.forward (prompt rows through the MFMA prefill GEMMs and the flash attention) whose
-logits[:-1] score inp[1:] with a summed cross entropy. ppl = exp(sum nll / tokens scored).
+logits[:-1] score inp[1:] with a summed cross entropy (LLaMA.window_nll: the per-row NLL kernel, summed in
+double on the device and read back once per text). ppl = exp(sum nll / tokens scored).
 
 The reference fetches wikitext / ptb / c4 with `datasets` (evaluate/full.py:23-43); without a
 network the text comes from files (`--text_path`, one or more, comma separated)."""
@@ -30,17 +31,18 @@ WINDOW = 2048  # reference evaluate/full.py:117 ("for compat with gptq")
 @torch.no_grad()
 def perplexity(model: LLaMA, encoded_text: torch.Tensor, window: int = WINDOW):
     """reference evaluate/full.py:114-128 over `encoded_text` (1, N) on the model's device:
-    returns (ppl, summed nll, tokens scored)."""
-    nlls, toks = 0.0, 0
+    returns (ppl, summed nll, tokens scored). Every window is scored on the device (LLaMA.window_nll:
+    the per-row NLL kernel over the window's logits) into one float64 (sum, count) pair that is read
+    back once, after the last window."""
     window = min(window, model.config.block_size)
+    total = torch.zeros(2, dtype=torch.float64, device=encoded_text.device)
     for i in range(0, encoded_text.shape[1], window):
         inp = encoded_text[:, i:i + window]
         if inp.shape[1] < 2:
             break
-        logits = model(inp)[0]
-        nll = torch.nn.functional.cross_entropy(logits[:-1].float(), inp[0, 1:].to(dtype=torch.long), reduction="sum")
-        toks += inp.size(1) - 1
-        nlls += nll.item()
+        model.window_nll(inp, total)
+    nlls, toks = total.tolist()
+    toks = int(toks)
     return math.exp(nlls / toks), nlls, toks
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h and the
-lit_llama_amd_lora.h it includes).
+lit_llama_amd_lora.h and lit_llama_amd_nll.h it includes).
 
 The library is the only compute path of this package: there is no CPU or eager-PyTorch
 fallback. If it is missing or the device is not a ROCm GPU, calls raise.
@@ -111,6 +111,13 @@ LORA_SIGNATURES = {
                           _F],
 }
 
+# the scoring entry points (include/lit_llama_amd_nll.h, which lit_llama_amd.h includes): (logits, ldl, M, V,
+# targets, row_nll, total, stream) over bf16 / fp32 logits. A table of its own, as the header is.
+NLL_SIGNATURES = {
+    "llj_nll": [_P, _I, _I, _I, _P, _P, _P, _P],
+    "llj_g_nll": [_P, _I, _I, _I, _P, _P, _P, _P],
+}
+
 _lib = None
 
 
@@ -133,7 +140,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no fallback path.")
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, argt in {**SIGNATURES, **LORA_SIGNATURES}.items():
+        for name, argt in {**SIGNATURES, **LORA_SIGNATURES, **NLL_SIGNATURES}.items():
             f = getattr(L, name)
             f.argtypes = argt
             f.restype = ctypes.c_int

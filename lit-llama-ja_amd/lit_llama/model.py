@@ -458,6 +458,26 @@ class LLaMA(nn.Module):
                              f"max_seq_length {S}; call reset_cache() first")
         return self._run(idx, pos, S, self.kv_caches, all_rows=True)
 
+    @torch.no_grad()
+    def window_nll(self, idx: torch.Tensor, total: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-token negative log-likelihood of one window (the scoring step of the evaluate scripts,
+        reference evaluate/full.py:119-123): the no-cache forward of idx (1, T >= 2), then rows 0..T-2 of
+        the logits scored against idx[0, 1:] on the device (llj_nll for bf16 logits, llj_g_nll for fp32
+        ones; logsumexp over the padded vocabulary, as F.cross_entropy on the reference's logits).
+        Returns the (T - 1,) fp32 values; `total`, a (2,) float64 device tensor, also receives
+        total[0] += their sum, total[1] += T - 1 in stream order, so many windows are read back once."""
+        B, T = idx.size()
+        assert B == 1 and T >= 2, "window_nll scores one sequence of at least 2 tokens"
+        logits = self(idx)[0]
+        targets = idx[0, 1:].to(torch.int32).contiguous()
+        out = torch.empty(T - 1, dtype=torch.float32, device=logits.device)
+        if total is not None:
+            _hip.require_device(total, "total")
+            assert total.dtype == torch.float64 and total.shape == (2,) and total.is_contiguous()
+        _hip.call("llj_g_nll" if logits.dtype == torch.float32 else "llj_nll", logits.data_ptr(), logits.stride(0),
+                  T - 1, logits.shape[1], targets.data_ptr(), out.data_ptr(), _hip.ptr(total), _hip.stream())
+        return out
+
     def _alloc_kv(self, B, S, device, n=None):
         hs = self.config.n_embd // self.config.n_head
         shape = (B, self.config.n_head, S, hs)
