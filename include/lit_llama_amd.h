@@ -403,7 +403,8 @@ int llj_g_linear_v2(int wkind, const void* x, int ldx, int M, int K, const void*
  * (model.py:204-228, 312-329); rope (block_size, hs/2, 2) fp32; head size even. */
 int llj_g_rope_kv(const void* qkv, void* q_out, void* kcache, void* vcache, const float* rope, const int* pos, int B, int T,
                   int C, int n_head, int S, int dt, void* stream);
-/* Causal attention as llj_attention, any head size ((S + hs) * 4 bytes of LDS <= 64 KiB). */
+/* Causal attention as llj_attention, any head size ((S + hs + 4) * 4 bytes of LDS <= 64 KiB: the
+ * scores, the scaled query and 4 words of reduction scratch; LLJ_EINVAL beyond). */
 int llj_g_attention(const void* q, const void* kcache, const void* vcache, void* y, const int* pos, int B, int T, int C,
                     int n_head, int S, int dt, void* stream);
 /* h[i] = silu(a1[i]) * a2[i], i < n (model.py:258-259; dt 0: bf16(bf16(silu(a1)) * a2)). */

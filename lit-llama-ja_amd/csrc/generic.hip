@@ -161,7 +161,8 @@ __global__ __launch_bounds__(64) void g_rope_kv_kernel(const TT* __restrict__ qk
 
 // ---- causal attention (model.py:237, the tril mask rows): row m at position p attends cache
 // slots [0, p] (all S slots once p >= S: the ring holds the last S positions). Scores in LDS,
-// fp32 softmax, y = P V / sum (rounded to bf16 on the bf16 path). Block (row, head); LDS: S + hs floats.
+// fp32 softmax, y = P V / sum (rounded to bf16 on the bf16 path). Block (row, head); LDS: S + hs floats
+// and the 4 static ones of the reductions.
 template <typename TT>
 __global__ __launch_bounds__(256) void g_attention_kernel(const TT* __restrict__ q, const TT* __restrict__ kc,
                                                           const TT* __restrict__ vc, TT* __restrict__ y,
@@ -453,7 +454,8 @@ int llj_g_attention(const void* q, const void* kcache, const void* vcache, void*
   LLJ_REQUIRE(q && kcache && vcache && y && pos && B > 0 && T > 0 && n_head > 0 && C % n_head == 0 && S > 0 &&
               (dt == 0 || dt == 1));
   const size_t lds = (size_t)(S + C / n_head) * 4;
-  LLJ_REQUIRE(lds <= 64 * 1024);
+  // the launch sets no larger LDS limit, so the kernel's static words (red[4]) count against the 64 KiB too
+  LLJ_REQUIRE(lds + 4 * sizeof(float) <= 64 * 1024);
   hipStream_t s = (hipStream_t)stream;
   LLJ_DT(dt, hipLaunchKernelGGL(g_attention_kernel<bf16_t>, dim3(B * T, n_head), dim3(256), lds, s, (const bf16_t*)q,
                                 (const bf16_t*)kcache, (const bf16_t*)vcache, (bf16_t*)y, pos, T, C, n_head, S),

@@ -208,8 +208,9 @@ def test_norm_swiglu_v2(hip, wfmt, M, sa):
         a1 = affine(linear(hip, wfmt, xd, W1d, s1, H, C), sc1, bi1).contiguous()
         a2 = affine(linear(hip, wfmt, xd, W2d, s2, H, C), sc2, bi2).contiguous()
         want = torch.empty(M, H, dtype=BF, device=dev)
+        # (here and below) the borrowed oracle is itself checked: tests/test_generic_kernels_gpu.py::test_silu_mul_*
         call(hip, "llj_g_silu_mul", a1.data_ptr(), a2.data_ptr(), want.data_ptr(), M * H, 0, st())
-        he = torch.empty(M, H, dtype=BF, device=dev)
+        he =torch.empty(M, H, dtype=BF, device=dev)
         call(hip, "llj_norm_swiglu", wfmt, xd.data_ptr(), None, 0.0, W1d.data_ptr(), P(s1), W2d.data_ptr(), P(s2),
              he.data_ptr(), M, H, C, None, 0, None, None, 0, st())
 
@@ -243,6 +244,7 @@ def rope_kv(hip, qkv, B, T_, nh, hs, S, rope, pos):
     q = torch.zeros(B * T_, Cd, dtype=BF, device=dev)
     kc = torch.zeros(B, nh, S, hs, dtype=BF, device=dev)
     vc = torch.zeros_like(kc)
+    # the borrowed oracle is itself checked against numpy: tests/test_generic_kernels_gpu.py::test_rope_kv_*
     call(hip, "llj_g_rope_kv", qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), rope.data_ptr(), pos.data_ptr(),
          B, T_, Cd, nh, S, 0, st())
     return q, kc, vc

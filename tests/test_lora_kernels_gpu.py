@@ -189,6 +189,7 @@ def test_norm_qkv_rope_lora(hip, wfmt, nh, B, sa):
             _, _, B0 = lora_ops(rng, r, en, C, zero_b=True)
             t = norm_linear(hip, 1, xd, gd, img, None, img.shape[0])
             assert t.shape[1] % 16 == 0 and (r != 4 or t.shape[1] == 16)  # r = 4: rows of t padded to 16
+            # (here and below) rope_kv is llj_g_rope_kv, itself checked: tests/test_generic_kernels_gpu.py::test_rope_kv_*
             want = rope_kv(hip, add_lora(y, t, Bd, r, en, scaling).contiguous(), B, 1, nh, hs, S, rope, pos)
             tail = (t.data_ptr(), t.stride(0), Bd.data_ptr(), r, mask_bits(en), scaling)
             got = fused("llj_norm_qkv_rope_lora", *tail)
