@@ -1,4 +1,6 @@
 """Shared test helpers: host-side statements of the device layouts and tolerance rules."""
+import functools
+
 import numpy as np
 
 from oracle import llama_np as O
@@ -218,3 +220,270 @@ def exact_sum_mask(v, width=16):
         tz += ((mi & ((1 << (s + 1)) - 1)) == 0) & (mi != 0)
     unit = (low + tz).min(-1)
     return t.sum(-1) < np.ldexp(1.0, (unit + 24).clip(-1000, 1000))
+
+
+# ------------------------------------------------------------------ exact LLM.int8 operands
+# Inputs for which the LLM.int8 kernels (wfmt 2) have one correct bit pattern (tests/test_int8_exact_gpu.py):
+# with SCA = 127 * 2^-j and SCB = 127 * 2^-e the fp32 dequantization constant SCA * SCB / 127^2 is exactly
+# 2^-(j + e) however it is associated, 127 / SCA = 2^j, SCB / 127 = 2^-e, so acc * const is exact in fp32
+# while |acc| < 2^24 and both fp16 roundings and the bf16 one are decided by the reference alone.
+I8_THR = 6.0
+I8_SUB = {5: 15, 6: 7, 14: 0}  # largest sub-threshold entry of an outlier column, in quarters, per SCA class
+
+
+def f16_bits(x):
+    return np.asarray(x).astype(np.float16).view(np.uint16)
+
+
+def _dyadic_unit(v):
+    """Per row of v (float64, dyadic): the largest power of two that every entry is a multiple of (1 for a
+    row of zeros)."""
+    u = np.ones(v.shape[0])
+    for p in range(1, 40):
+        frac = v * 2.0 ** (p - 1)
+        u = np.where((frac != np.rint(frac)).any(1), 2.0 ** -p, u)
+    return u
+
+
+def i8_reference(a, cb, e, thr=I8_THR, mutate=None):
+    """LLM.int8 of activations a (M, K) on codes cb (N, K) int8 and SCB[n] = 127 * 2^-e[n], in integers and
+    float64: outlier set O = columns with any |a| >= thr, SCA[m] = max |a| over the elements below thr (which
+    must be 127 * 2^-j or 0), codes = rint-even(a * 127 / SCA) with O zeroed, main16 = f16(acc * 2^-(j + e)),
+    side = sum_{k in O} a CB 2^-e, y16 = f16(main16 + side). Asserts the conditions under which a correct
+    kernel has exactly these bits. mutate: None, or the wrong reference "inner" / "outer" (that fp16 rounding
+    dropped), "dropcol" (the last outlier column left out of the side product), "halfaway" (code ties rounded
+    away from zero). Returns a dict; `y16` float32 (fp16 values; "outer": not rounded to fp16)."""
+    f32, f64 = np.float32, np.float64
+    a = np.asarray(a, f32)
+    assert np.array_equal(bf16(a), a) and np.array_equal(a.astype(np.float16).astype(f32), a), "a: not bf16 and fp16 values"
+    a64, cb64, e = a.astype(f64), np.asarray(cb, f64), np.asarray(e)
+    big = np.abs(a64) >= thr
+    O = big.any(0)
+    sca = np.where(big, 0.0, np.abs(a64)).max(1)
+    mant, ex = np.frexp(sca)
+    assert np.all((sca == 0) | (mant == 127.0 / 128)), f"SCA is not 127 * 2^-j: {sca}"
+    j = np.where(sca > 0, 7 - ex, 0)
+    inv = np.where(sca > 0, 2.0 ** j, 0.0)
+    # the fp32 constants the kernels form, in each association
+    sa32, scb32, kq = sca.astype(f32)[:, None], (127.0 * 2.0 ** -e).astype(f32)[None, :], f32(1.0) / (f32(127.0) * f32(127.0))
+    const = np.where(sca > 0, 2.0 ** -j, 0.0)[:, None] * 2.0 ** -e[None, :]
+    assert np.array_equal(scb32.astype(f64), 127.0 * 2.0 ** -e[None, :])
+    for got in ((sa32 * scb32) * kq, sa32 * (scb32 * kq), (sa32 * scb32) / f32(16129.0)):
+        assert got.dtype == f32 and np.array_equal(got.astype(f64), const), "the dequantization constant is not 2^-(j + e)"
+    assert np.array_equal((f32(127.0) / np.where(sca > 0, sca, 1.0).astype(f32)).astype(f64), np.where(sca > 0, inv, 127.0))
+    assert np.array_equal((scb32 / f32(127.0)).astype(f64), 2.0 ** -e[None, :])
+    x = a64 * inv[:, None]
+    codes = np.sign(x) * np.floor(np.abs(x) + 0.5) if mutate == "halfaway" else np.rint(x)
+    codes[:, O] = 0
+    assert np.abs(codes).max(initial=0) <= 127
+    acc = codes @ cb64.T
+    assert np.abs(acc).max() < 2.0 ** 24, f"|acc| = {np.abs(acc).max()} >= 2^24"
+    main = acc * const
+    main16 = main.astype(np.float16).astype(f64)
+    cols = np.nonzero(O)[0]
+    if mutate == "dropcol":
+        cols = cols[:-1]
+    w = cb64 * 2.0 ** -e[:, None]
+    assert np.array_equal(w.astype(np.float16).astype(f64), w)
+    ao = a64[:, cols]
+    side = ao @ w[:, cols].T
+    unit = _dyadic_unit(ao)
+    worst = ((np.abs(ao) / unit[:, None]) @ np.abs(cb64[:, cols]).T).max(initial=0)
+    assert worst < 2.0 ** 24, f"side product: sum |a| |CB| = {worst} units >= 2^24"
+    if mutate == "inner":
+        s32 = (main.astype(f32) + side.astype(f32)).astype(f32)
+    else:
+        s32 = (main16 + side).astype(f32)
+        assert np.array_equal(s32.astype(f64), main16 + side), "main16 + side is not exact in fp32"
+    y16 = s32 if mutate == "outer" else s32.astype(np.float16).astype(f32)
+    assert np.abs(s32).max() < 65504.0
+    return dict(O=O, cols=np.nonzero(O)[0], sca=sca.astype(f32), j=j, codes=codes.astype(np.int8), acc=acc, main=main,
+                side=side, y16=y16)
+
+
+def i8_exact_case(M, N, K, ocols, j_rows, seed, hot=None, rowmax_in_outlier=False, e_lo=3, e_hi=9, mutants=True,
+                  wseed=0):
+    """Exact LLM.int8 operands. Row m has SCA class j_rows[m] in {5, 6, 14} (SCA = 127 * 2^-j; 14: below 1 / 64,
+    the GEMV's quant8f rule): elements n * 2^-(j + 1), |n| <= 254 (bf16 values; about half the codes are ties,
+    which pins round-to-nearest-even), one element +-127 * 2^-j off the outlier columns. Outlier columns
+    `ocols`: one or two rows (`hot`: a list of row lists per column; never a class-14 row) hold +-6 (the
+    threshold itself), +-8 or +-12, the others sub-threshold multiples of 1 / 4 no larger than their SCA (0 in a
+    class-14 row: its main term reaches down to 2^-23, which no fp32 sum with a side term holds exactly).
+    rowmax_in_outlier: a row's only +-127 * 2^-j sits in the first outlier column, below the threshold, where
+    another row sets the outlier, and the rest of that row stays strictly below it (asserted; `rowmax_row` names
+    the row): that element alone decides SCA, and its code is zeroed. CB: int8 over -127 .. 127;
+    SCB[n] = 127 * 2^-e, e in e_lo .. e_hi (drawn from (N, K, seed, wseed) only: the activations do not depend on
+    N or wseed). Returns the operands, i8_reference's fields and, with `mutants`,
+    `wrong`: the y16 of each wrong reference."""
+    rng = np.random.default_rng([61, M, K, len(ocols), seed])
+    j = np.asarray(j_rows, np.int64)
+    assert j.shape == (M,) and set(j.tolist()) <= set(I8_SUB)
+    ocols = np.unique(np.asarray(ocols, np.int64))
+    assert ocols.size == 0 or (0 <= ocols[0] and ocols[-1] < K)
+    free = np.setdiff1d(np.arange(K), ocols)
+    a = rng.integers(-254, 255, size=(M, K)) * 2.0 ** -(j + 1)[:, None]
+    kmax = rng.choice(free, M)
+    a[np.arange(M), kmax] = 127 * 2.0 ** -j * rng.choice([-1.0, 1.0], M)
+    setters = np.nonzero(j != 14)[0]
+    assert ocols.size == 0 or setters.size, "outlier columns need a row of class 5 or 6 to set them"
+    lim = np.array([I8_SUB[v] for v in j.tolist()])
+    hots = []
+    for i, c in enumerate(ocols):
+        a[:, c] = rng.integers(-lim, lim + 1) / 4.0
+        nh = 1 if (rowmax_in_outlier and i == 0) else min(setters.size, int(rng.integers(1, 3)))
+        h = np.asarray(hot[i]) if hot is not None else rng.choice(setters, nh, replace=False)
+        a[h, c] = rng.choice([6.0, -6.0, 8.0, -8.0, 12.0, -12.0], h.size)
+        hots.append(h)
+    rowmax_row = None
+    if rowmax_in_outlier:
+        # every other element of that row stays strictly below the maximum (|n| <= 253; |n| = 254 is 127 * 2^-j
+        # too), so the element inside the outlier column alone decides the row's SCA
+        r = rowmax_row = [m for m in setters if m not in hots[0]][0]
+        top = 127 * 2.0 ** -j[r]
+        a[r, free] = np.where(np.abs(a[r, free]) >= top, np.sign(a[r, free]) * 253 * 2.0 ** -(j[r] + 1), a[r, free])
+        a[r, ocols[0]] = top * rng.choice([-1.0, 1.0])
+        inside = np.abs(a[r, ocols])
+        assert inside[inside < I8_THR].max() == top > np.abs(a[r, free]).max(), "the row maximum is not inside O alone"
+    a = a.astype(np.float32)
+    rng = np.random.default_rng([62, N, K, seed, wseed])
+    cb = rng.integers(-127, 128, size=(N, K)).astype(np.int8)
+    e = rng.integers(e_lo, e_hi + 1, size=N)
+    c = dict(a=a, cb=cb, e=e, scb=(127.0 * 2.0 ** -e).astype(np.float32), M=M, N=N, K=K, rowmax_row=rowmax_row)
+    c.update(i8_reference(a, cb, e))
+    assert np.array_equal(c["cols"], ocols) and np.array_equal(c["j"], j)
+    if mutants:
+        c["wrong"] = {m: i8_reference(a, cb, e, mutate=m)["y16"] for m in ("inner", "outer", "halfaway")
+                      + (("dropcol",) if ocols.size else ())}
+    return c
+
+
+class I8Power:
+    """Test power over the cases of one test, from the references alone: the share of the pooled bf16 (or, dt 1,
+    fp16) outputs in which each wrong reference differs from the right one. The floors: a dropped fp16 rounding
+    >= 1 % and >= 8 elements (fp16 output, inner: >= 10 %), a dropped outlier column or ties rounded half away
+    >= 50 %. The fp16 roundings and the dropped column count over the cases with outlier columns only
+    (without a side term the two fp16 roundings are one)."""
+
+    def __init__(self, out=bf16):
+        self.out, self.d = out, {}
+
+    def add(self, c):
+        right = self.out(c["y16"])
+        for m, y in c["wrong"].items():
+            if m in ("inner", "outer") and not c["cols"].size:
+                continue
+            self.d.setdefault(m, []).append((self.out(y) != right).ravel())
+
+    def shares(self):
+        return {m: (float(np.mean(np.concatenate(v))), int(np.sum(np.concatenate(v)))) for m, v in self.d.items()}
+
+    def finish(self, what, need=("inner", "outer", "dropcol", "halfaway")):
+        s = self.shares()
+        print(f"{what}: wrong-reference shares " + ", ".join(f"{m} {s[m][0]:.3f} ({s[m][1]})" for m in s))
+        for m in need:
+            share, n = s[m]
+            if m in ("inner", "outer"):
+                floor = 0.10 if (m == "inner" and self.out is not bf16) else 0.01
+                assert share >= floor and n >= 8, f"{what}: {m} fp16 rounding dropped differs in {share:.4f} ({n} elements)"
+            else:
+                assert share >= 0.5, f"{what}: {m} differs in only {share:.4f}"
+        return s
+
+
+# The input families of tests/test_int8_exact_gpu.py (tests/test_int8_exact_host.py checks every one against
+# the oracle on the CPU). GEMV side-product regimes: name -> (K, outlier columns); each is the smallest shape
+# that reaches the code named (csrc/gemv_impl.h).
+def _i8_gemv_layouts():
+    rng = np.random.default_rng(77)
+    pick = lambda lo, width, n: sorted((lo + rng.choice(width, n, replace=False)).tolist())  # noqa: E731
+    ins = [0, 127, 128 + 15, 256 + 16, 256 + 63, 640 + 64, 3072 + 63, 3072 + 127]
+    walk = [3, 16 + 2, 64 + 16 + 5, 32 + 0, 32 + 15, 64 + 32 + 7, 64 + 48 + 9]  # lane groups 0..3: 1, 2, 3, 1 columns
+    return {
+        "none": (128, []),
+        # K = 3200: k-block width 128 = the chunk, so the side product runs inside the weight stream from the
+        # one-launch prep's aval table: 0, 1 and 2 columns per chunk, the first and the last chunk
+        "instream": (3200, ins),
+        "instream_over": (3200, ins + [896 + 1, 896 + 40, 896 + 100]),  # a chunk with 3: after the stream
+        # one k-block of 32 with exactly SPC = 8 columns (4 waves: the fast path), then 9 (the general list walk)
+        "spc8": (128, pick(32, 32, 8)),
+        "spc9": (128, pick(32, 32, 9)),
+        # K = 8192: 8-wave residual form, SPC = 32 of a k-block of 256
+        "spc32w8": (8192, pick(768, 256, 32)),
+        "spc33w8": (8192, pick(768, 256, 33)),
+        # one full kSideChunk = 256 round, one entry into the second, 300
+        "rounds256": (640, pick(0, 640, 256)),
+        "rounds257": (640, pick(0, 640, 257)),
+        "rounds300": (640, pick(0, 640, 300)),
+        # AM_I8Q's walk over the weight registers: lane group g holds k = 64 t + 16 g + 0..15 of a chunk; groups
+        # with 1, 2 and 3 columns (two per trip plus an odd one), every group, both MFMA steps t; 32 in a chunk
+        "walk128": (128, walk),
+        "walk128x32": (128, pick(0, 128, 32)),
+        "walk640": (640, [walk[0]] + [128 + k for k in walk[1:3]] + [256 + k for k in walk[3:6]] + [384 + walk[6]]
+                    + pick(512, 128, 32)),
+    }
+
+
+I8_GEMV_LAYOUTS = _i8_gemv_layouts()
+I8_ROW_CLASSES = (5, 6, 14, 5, 6, 5, 6, 5)
+
+
+def i8_rows(M, with14=True):
+    """SCA classes of M rows: 5 and 6 alternating, every eighth row from the third on 14 (M >= 3)."""
+    if M <= 2 or not with14:
+        return tuple(np.resize((5, 6), M).tolist())
+    return tuple(np.resize(I8_ROW_CLASSES, M).tolist())
+
+
+@functools.lru_cache(maxsize=None)
+def i8_gemv_case(layout, M, N, seed=0, e_lo=3, e_hi=9, wseed=0, with14=True):
+    K, ocols = I8_GEMV_LAYOUTS[layout]
+    return i8_exact_case(M, N, K, ocols, i8_rows(M, with14), seed, rowmax_in_outlier=M > 1 and len(ocols) > 0, e_lo=e_lo,
+                         e_hi=e_hi, wseed=wseed)
+
+
+@functools.lru_cache(maxsize=None)
+def i8_quant8f_case(M, N, K):
+    """Rows of class 14 only (SCA < 1 / 64 in every row), no outlier columns."""
+    return i8_exact_case(M, N, K, [], (14,) * M, 3)
+
+
+# the prefill GEMM: (outlier columns, gather capacity kpad or None); the last outlier column of a case is set by
+# one row alone (i8_gemm_case)
+I8_GEMM_SIDES = [(0, None), (3, None), (32, None), (33, None), (70, None), (70, 128), (64, 64), (70, 64), (3, 64)]
+
+
+@functools.lru_cache(maxsize=None)
+def i8_gemm_case(M, N, K, ncols, wseed=0, e_lo=3, e_hi=9):
+    rng = np.random.default_rng([78, M, K, ncols])
+    ocols = np.sort(rng.choice(K, ncols, replace=False))
+    rows = np.array(i8_rows(M))
+    setters = np.nonzero(rows != 14)[0]
+    hot = [rng.choice(setters, int(rng.integers(1, 3)), replace=False) for _ in range(ncols)]
+    if ncols:
+        hot[-1] = setters[-1:]  # an outlier column that a single row sets
+    return i8_exact_case(M, N, K, ocols, rows, 0, hot=hot, rowmax_in_outlier=ncols > 0, wseed=wseed, e_lo=e_lo, e_hi=e_hi)
+
+
+I8_GENERIC_SHAPES = [(1, 20, 6, 2), (7, 780, 36, 30), (40, 132, 10, 5)]  # (M, K, N, outlier columns)
+
+
+@functools.lru_cache(maxsize=None)
+def i8_generic_case(M, K, N, ncols):
+    rng = np.random.default_rng([79, M, K, N])
+    return i8_exact_case(M, N, K, rng.choice(K, ncols, replace=False), i8_rows(M), 0, rowmax_in_outlier=M > 1)
+
+
+def i8_zero_row_case(M, N, K):
+    """A case whose last row is all zero (SCA 0: codes 0, output 0) -- alone at M = 1 -- next to rows with outliers."""
+    c = i8_exact_case(max(M, 2), N, K, [7, 90], i8_rows(max(M, 2), False), 9, hot=[[0], [0]], mutants=False)
+    a = c["a"][:M].copy()
+    a[M - 1] = 0.0
+    c = dict(c, a=a, M=M, rowmax_row=None)
+    c.update(i8_reference(a, c["cb"], c["e"]))
+    assert c["sca"][M - 1] == 0 and not c["y16"][M - 1].any()
+    return c
+
+
+def i8_has_rowmax(cases):
+    """At least one of a test's cases has a row whose SCA is decided inside an outlier column another row sets."""
+    return any(c["rowmax_row"] is not None for c in cases)

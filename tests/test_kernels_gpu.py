@@ -242,11 +242,16 @@ def test_bf16_linear(hip, M, N, K):
 @pytest.mark.parametrize("outliers", [0, 3, 120, 300, 700])
 @pytest.mark.parametrize("M", [1, 8])
 def test_int8_linear_vs_restatement(hip, M, outliers):
-    """LLM.int8() against the oracle's restatement (bitsandbytes absent: parity unpinned). At K 4096
-    the side product runs inside the weight stream from the prep's aval table (3 columns: within
-    the entries prefetched per chunk; 120: past them, ~4 per chunk); 300 outlier columns (about what
-    the synthetic 7B down projection sees at bs=8, K 11008) run it after the stream from the LDS
-    stash of CB bytes; 700 (> kStashCols = 512) also the global-read tail."""
+    """LLM.int8() against the oracle's restatement (bitsandbytes absent: parity unpinned). Which
+    side-product path a case takes follows from its outlier counts per k-block (csrc/gemv_impl.h). At
+    K 4096 the k-blocks are the 128-deep chunks: with at most 2 outlier columns in every chunk (the 3
+    columns) the side product runs inside the weight stream from the prep's aval table; with more it
+    runs after the stream in i8_side_tile, on the fast path while every k-block holds at most SPC = 8
+    columns (4 waves: the speculatively loaded list entries; 120 columns at M 1, at most 6 per
+    k-block) and on the general list walk beyond (120 columns at M 8: one k-block holds 11). At K 11008
+    (k-blocks of 352) the 300 and 700 columns take the general walk, in one to three rounds of
+    kSideChunk = 256 -- a scaled column is an outlier only where some row reaches 6.0, so fewer columns
+    are flagged than scaled (300 at M 1: 249, one round)."""
     rng = np.random.default_rng(M + 100 * outliers)
     N, K = (256, 4096) if outliers <= 120 else (256, 11008)
     W = bf16(rng.standard_normal((N, K)) * 0.02)
@@ -1662,8 +1667,11 @@ def test_gemm_grouped_dequant_equals_get_weight_bf16(hip, scale_kind):
         sc = bf16(sc)
     x = np.eye(K, dtype=np.float32)
     out = torch.empty(K, N, dtype=torch.bfloat16, device=dev)
-    call(hip, "llj_gemm_linear", 4 | (1 << 8), T(x, torch.bfloat16).data_ptr(), K, repack(hip, qw).data_ptr(),
-         sz_grouped(hip, sc, z).data_ptr(), out.data_ptr(), N, K, N, K, st())
+    # the operands stay referenced until the launch: a temporary freed after .data_ptr() hands its block to the
+    # next allocation in the same argument list, which then overwrites the identity
+    xd, Wd, szd = T(x, torch.bfloat16), repack(hip, qw), sz_grouped(hip, sc, z)
+    call(hip, "llj_gemm_linear", 4 | (1 << 8), xd.data_ptr(), K, Wd.data_ptr(), szd.data_ptr(), out.data_ptr(), N, K, N, K,
+         st())
     torch.cuda.synchronize()
     wref = O.colblock_get_weight(qw, sc, z, 4, tile_cols=g, bf16=True)
     np.testing.assert_array_equal(out.float().cpu().numpy().T, wref)
