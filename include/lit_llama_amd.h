@@ -498,4 +498,8 @@ int llj_stream_read(const void* p, size_t bytes, float* out, int grid, void* str
 /* The scoring entry points (llj_nll, llj_g_nll: per-token negative log-likelihood over logits) likewise. */
 #include "lit_llama_amd_nll.h"
 
+/* The entry points for sampling one prompt many times (llj_attention_shared: decode attention of rows that
+ * share a prompt prefix) likewise. */
+#include "lit_llama_amd_samples.h"
+
 #endif /* LIT_LLAMA_AMD_H */

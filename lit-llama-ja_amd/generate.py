@@ -6,6 +6,9 @@ sampling, EOS returns idx[:input_pos] (the EOS token itself is NOT included). Ev
 step runs as one captured HIP graph replay: greedy (top_k=1) ends in the argmax kernel, other
 top_k / temperatures in the device top-k sampler.
 
+`generate_samples()` (CLI: --batch_samples) produces the num_samples continuations of one prompt as one batch:
+one prefill, every row its own draws, one decode step for all rows (DecodeSession.prefill_shared).
+
 CLI flags follow reference generate.py:92-102 (argparse; jsonargparse is not installed).
 The default CLI decode (top_k=200, temperature=0.8) runs the same captured graph as greedy, with
 the device sampler (llj_sample) in place of the argmax.
@@ -92,10 +95,50 @@ def generate_batch(model: LLaMA, idx: torch.Tensor, max_new_tokens: int, *, max_
     return rows
 
 
+@torch.no_grad()
+def generate_samples(model: LLaMA, idx: torch.Tensor, num_samples: int, max_new_tokens: int, *,
+                     max_seq_length: Optional[int] = None, temperature: float = 1.0, top_k: Optional[int] = None,
+                     eos_id: Optional[int] = None) -> list:
+    """num_samples continuations of one 1-D prompt as one batch: the prompt is prefilled once
+    (DecodeSession.prefill_shared), every row draws its own tokens (the uniform of row b at position p is
+    hash(seed, p, b), the seed drawn from torch's default generator as in generate()), and a decode step
+    serves all rows. Returns a list of num_samples 1-D tensors, each cut by the reference's EOS rule (the EOS
+    token itself excluded); with eos_id the host looks at the ids every EOS_CHECK_EVERY steps and stops once
+    every row has one. top_k == 1 is greedy: all rows equal."""
+    if num_samples < 1:
+        raise ValueError(f"num_samples {num_samples} < 1")
+    T = idx.size(0)
+    T_new = T + max_new_tokens
+    if max_seq_length is None:
+        max_seq_length = min(T_new, model.config.block_size)
+    if max_new_tokens <= 0:
+        return [idx.clone() for _ in range(num_samples)]
+    seed = 0 if top_k == 1 else int(torch.randint(0, 2 ** 62, (1,)))
+    sess = DecodeSession(model, num_samples, max_seq_length, T_new, temperature=temperature, top_k=top_k, seed=seed)
+    sess.prefill_shared(idx)
+    left = max_new_tokens - 1
+    while left:
+        if eos_id is not None and bool((sess.output()[:, T:] == eos_id).any(dim=1).all()):
+            break
+        n = min(left, EOS_CHECK_EVERY) if eos_id is not None else left
+        sess.decode(n)
+        left -= n
+    out = sess.output().to(idx.dtype)
+    if eos_id is None:
+        return list(out.unbind(0))
+    rows = []
+    for b in range(num_samples):
+        hit = (out[b, T:] == eos_id).nonzero()
+        rows.append(out[b, :T + int(hit[0, 0])] if hit.numel() else out[b])
+    return rows
+
+
 def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tokens: int = 50, top_k: int = 200,
          temperature: float = 0.8, checkpoint_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
-         tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None) -> None:
-    """Generates text samples based on a pre-trained LLaMA model and tokenizer (reference generate.py:92-155)."""
+         tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
+         batch_samples: bool = False) -> None:
+    """Generates text samples based on a pre-trained LLaMA model and tokenizer (reference generate.py:92-155).
+    batch_samples: the num_samples samples as one batch (generate_samples) instead of one after the other."""
     assert checkpoint_path.is_file(), checkpoint_path
     assert tokenizer_path.is_file(), tokenizer_path
     if not torch.cuda.is_available():
@@ -114,6 +157,20 @@ def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tok
     encoded = tokenizer.encode(prompt, bos=True, eos=False, device=torch.device("cuda"))
     prompt_length = encoded.size(0)
     torch.manual_seed(1234)
+    if batch_samples:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_samples(model, encoded, num_samples, max_new_tokens, temperature=temperature, top_k=top_k)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        model.reset_cache()
+        for y in ys:
+            print(tokenizer.decode(y))
+        tokens_generated = sum(y.size(0) - prompt_length for y in ys)
+        print(f"Time for inference of {num_samples} samples: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec",
+              file=sys.stderr)
+        print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+        return
     for i in range(num_samples):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -137,7 +194,9 @@ if __name__ == "__main__":
     ap.add_argument("--checkpoint_path", type=Path, default=Path("checkpoints/lit-llama/7B/lit-llama.pth"))
     ap.add_argument("--tokenizer_path", type=Path, default=Path("checkpoints/lit-llama/tokenizer.model"))
     ap.add_argument("--quantize", default=None, choices=[None, "llm.int8", "gptq.int4", "gptq.int8"])
+    ap.add_argument("--batch_samples", action="store_true",
+                    help="generate the num_samples samples as one batch: the prompt is prefilled once")
     a = ap.parse_args()
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_path=a.checkpoint_path, tokenizer_path=a.tokenizer_path,
-         quantize=a.quantize)
+         quantize=a.quantize, batch_samples=a.batch_samples)

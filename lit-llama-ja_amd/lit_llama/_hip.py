@@ -1,5 +1,5 @@
 """ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h and the
-lit_llama_amd_lora.h and lit_llama_amd_nll.h it includes).
+lit_llama_amd_lora.h, lit_llama_amd_nll.h and lit_llama_amd_samples.h it includes).
 
 The library is the only compute path of this package: there is no CPU or eager-PyTorch
 fallback. If it is missing or the device is not a ROCm GPU, calls raise.
@@ -118,6 +118,14 @@ NLL_SIGNATURES = {
     "llj_g_nll": [_P, _I, _I, _I, _P, _P, _P, _P],
 }
 
+# the entry points for sampling one prompt many times (include/lit_llama_amd_samples.h, which lit_llama_amd.h
+# includes): decode attention over a shared prompt prefix and its workspace size (returns size_t). A table of
+# its own, as the header is.
+SAMPLES_SIGNATURES = {
+    "llj_attention_shared_ws_bytes": [_I, _I, _I, _I],
+    "llj_attention_shared": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+}
+
 _lib = None
 
 
@@ -144,6 +152,10 @@ def lib() -> ctypes.CDLL:
             f = getattr(L, name)
             f.argtypes = argt
             f.restype = ctypes.c_int
+        for name, argt in SAMPLES_SIGNATURES.items():
+            f = getattr(L, name)
+            f.argtypes = argt
+            f.restype = ctypes.c_size_t if name.endswith("_ws_bytes") else ctypes.c_int
         L.llj_i8_ws_bytes.argtypes = [_I, _I]
         L.llj_i8_ws_bytes.restype = ctypes.c_size_t
         L.llj_attention_ws_bytes.argtypes = [_I, _I, _I, _I]

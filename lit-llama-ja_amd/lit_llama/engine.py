@@ -19,6 +19,7 @@ from __future__ import annotations
 import torch
 
 from . import _hip
+from . import model as _model
 from .model import LLaMA, _Work
 
 
@@ -92,16 +93,61 @@ class DecodeSession:
         self._choose(st)
         self.t_prompt = T
         self.steps_done = 1
-        # decode-step operands (fixed for the session)
+        self._setup_work()
+
+    def _setup_work(self, shared_prefix: int = 0) -> None:
+        """decode-step operands (fixed for the session); shared_prefix: see prefill_shared"""
+        m, B = self.model, self.B
         self.specs = m._layer_specs()
         if m._generic():  # the any-shape kernels (csrc/generic.hip)
             self.work = _Work(m.config, B, self.dev, False, self.S, generic=True, dtype=m.act_dtype(),
                               lora_cols=self.specs.get("lora_cols", 0))
         else:
             need_i8 = any(s[0] == 2 for layer in self.specs["layers"] for s in layer) or self.specs["head"][0] == 2
-            self.work = _Work(m.config, B, self.dev, need_i8, self.S, lora_cols=self.specs.get("lora_cols", 0))
+            self.work = _Work(m.config, B, self.dev, need_i8, self.S, lora_cols=self.specs.get("lora_cols", 0),
+                              shared_prefix=shared_prefix)
             m._enable_i8_handoff(self.work, self.specs)
+            if self.work.i8s:  # the attention is llj_attention_i8 (it hands y's statistics on): no shared route
+                self.work.shared_prefix, self.work.shared_ws = 0, None
         self.graph = None  # the caches / operands may have changed
+
+    @torch.no_grad()
+    def prefill_shared(self, prompt: torch.Tensor) -> None:
+        """prefill() for one prompt (1-D or (1, T)) that all B rows continue: the prompt runs once, as one row,
+        into row 0 of the caches; its T slots are copied to the other rows and its last-position logits to
+        all B rows of self.logits, from which every row draws its own first token (row b with hash(seed, pos,
+        b) or uniforms[T, b]). The caches then hold what prefill(prompt.repeat(B, 1)) leaves up to the
+        row count of the prefill launches, so every model kind decodes from them. Where the per-row decode
+        attention would be llj_attention / llj_attention_split (streaming kernels, bf16; not an adapter
+        prefix layer, the LLM.int8 hand-off or ATT_MERGE), the ring cannot wrap (total_len <= S) and
+        T >= model.SHARED_PREFIX_MIN, the decode steps run llj_attention_shared instead, which reads the
+        prompt's keys and values from row 0 only: work.shared_prefix = T, else 0."""
+        m, B = self.model, self.B
+        prompt = prompt.reshape(1, -1)
+        T = prompt.shape[1]
+        assert T >= 1 and T + 1 <= self.total
+        m.reset_cache()
+        m.kv_caches = m._alloc_kv(B, self.S, self.dev)
+        if m.rope_cache is None:
+            m.rope_cache = m.build_rope_cache(prompt)
+        pos = torch.arange(T, device=self.dev, dtype=torch.int32)
+        row0 = [(kc[:1], vc[:1]) for kc, vc in m.kv_caches]  # contiguous views: a one-row cache
+        m._run(prompt.to(self.dev), pos, self.S, row0, last_only_out=self.logits[:1])
+        if B > 1:
+            # token t lives in slot t % S; a prompt longer than the ring fills every slot
+            n = min(T, self.S)
+            for kc, vc in m.kv_caches:
+                kc[1:, :, :n] = kc[:1, :, :n]
+                vc[1:, :, :n] = vc[:1, :, :n]
+            self.logits[1:] = self.logits[:1]
+        st = _hip.stream()
+        self.tokens[:, :T] = prompt.to(torch.int32)
+        self.pos.fill_(T - 1)
+        self._choose(st)
+        self.t_prompt = T
+        self.steps_done = 1
+        shared = T if (self.total <= self.S and T >= _model.SHARED_PREFIX_MIN) else 0
+        self._setup_work(shared)
 
     def _reset_handoff(self):
         """The LLM.int8 hand-off blocks (_Work.y_st / h_st) must be zero when a step starts; a

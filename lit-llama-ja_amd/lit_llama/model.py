@@ -111,6 +111,26 @@ FLASH_MIN_T = 32
 ATT_MERGE = 0
 
 
+# one prompt sampled B times (DecodeSession.prefill_shared): prompts of at least SHARED_PREFIX_MIN tokens decode
+# through llj_attention_shared, which reads the prompt's keys / values from row 0's cache once per group of 8
+# rows; shorter ones run the per-row kernels on the copied caches. 64: the shortest prompt measured, and the
+# shared kernel already wins there (7B gptq.int4, 8 rows, S = 2048, ms per step copied caches / shared: P = 64
+# 1.707 / 1.689, 512 2.057 / 1.814, 1024 2.430 / 1.966, 1900 3.009 / 2.146; run-to-run spread of the former
+# <= 0.006; profiles/shared_prefix_ab.json)
+SHARED_PREFIX_MIN = 64
+# its prefix key ranges: SHARED_SPLIT_KEYS keys (one pass of a block) each while that makes at most SHARED_BLOCKS
+# prefix blocks (one per CU), longer ranges beyond. 7B gptq.int4, 8 rows, S = 2048, ms per step at 256 / 512 /
+# 1024 blocks: P = 1024 1.980 / 2.066 / 2.065, P = 1900 2.173 / 2.253 / 2.570
+SHARED_SPLIT_KEYS = 64
+SHARED_BLOCKS = 256
+
+
+def shared_splits(P: int, n_head: int, rows: int) -> int:
+    """prefix key ranges per (head, row group) of llj_attention_shared for a shared prompt of P tokens."""
+    cap = max(1, SHARED_BLOCKS // (n_head * ((rows + 7) // 8)))
+    return max(1, min(64, cap, (P + SHARED_SPLIT_KEYS - 1) // SHARED_SPLIT_KEYS))
+
+
 def attn_splits(S: int) -> int:
     """key ranges per (row, head) for a cache of S slots (1 = the one-block attention)."""
     if S < ATTN_SPLIT_MIN_S:
@@ -315,9 +335,12 @@ class _Work:
     """Per-call scratch for M rows (allocated from torch's caching allocator)."""
 
     def __init__(self, cfg: LLaMAConfig, M: int, device, need_i8: bool, S: int = 0, gemm: bool = False,
-                 generic: bool = False, dtype=torch.bfloat16, lora_cols: int = 0):
+                 generic: bool = False, dtype=torch.bfloat16, lora_cols: int = 0, shared_prefix: int = 0):
         C, H = cfg.n_embd, MLP.hidden(cfg)
         bf = torch.bfloat16
+        # decode rows whose caches share their first shared_prefix slots (DecodeSession.prefill_shared); 0: none
+        self.shared_prefix = 0
+        self.shared_ws = None
         self.generic = generic  # the any-shape kernels (LLaMA._blocks_generic)
         self.dt = _dt_code(dtype)
         # unmerged LoRA: t = rms_1(x) . lora_A^T (M, lora_cols), padded in columns to what the kernel that
@@ -384,6 +407,14 @@ class _Work:
         if self.att_merge:
             nb = _hip.lib().llj_attention_ws_bytes(1, cfg.n_head, C // cfg.n_head, self.att_merge)
             self.att_part = torch.empty(nb, dtype=torch.uint8, device=device)
+        # rows sharing a prompt prefix: partials of llj_attention_shared, which LLaMA._attention launches in
+        # place of llj_attention / llj_attention_split (ATT_MERGE and the LLM.int8 hand-off attention do not go
+        # through _attention: not with the former, and the session drops the route when the latter is enabled)
+        if shared_prefix > 0 and not gemm and not self.att_merge:
+            self.shared_prefix = shared_prefix
+            self.shared_split = shared_splits(shared_prefix, cfg.n_head, M)
+            nb = _hip.lib().llj_attention_shared_ws_bytes(M, cfg.n_head, C // cfg.n_head, self.shared_split)
+            self.shared_ws = torch.empty(nb, dtype=torch.uint8, device=device)
 
 
 class LLaMA(nn.Module):
@@ -638,6 +669,10 @@ class LLaMA(nn.Module):
             ak, av, gate, aT = ad
             _hip.call("llj_attention_adapter", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
                       pos.data_ptr(), B, T, nh, C // nh, S, ak.data_ptr(), av.data_ptr(), gate.data_ptr(), aT, st)
+            return
+        if ad is None and T == 1 and w.shared_prefix > 0 and not w.flash:  # rows of one prompt (prefill_shared)
+            _hip.call("llj_attention_shared", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
+                      pos.data_ptr(), B, w.shared_prefix, nh, C // nh, S, w.shared_split, w.shared_ws.data_ptr(), st)
             return
         if w.flash:
             _hip.call("llj_attention_prefill", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
