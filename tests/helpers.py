@@ -222,6 +222,144 @@ def exact_sum_mask(v, width=16):
     return t.sum(-1) < np.ldexp(1.0, (unit + 24).clip(-1000, 1000))
 
 
+# ------------------------------------------------------------------ exact epilogue operands
+# The adapter v2 affine and the unmerged LoRA term on top of an exact Linear (tests/test_epilogue_exact_gpu.py,
+# conditions checked on the CPU by tests/test_epilogue_exact_host.py): operands for which every fp32 sum and
+# product between two bf16 roundings is exact, so each rounding point alone decides the bits.
+def _col_mag(y):
+    """Per column of the exact y (M, N): the power of two nearest the mean |y| (1 for a column of zeros)."""
+    m = np.abs(np.asarray(y, np.float64)).mean(0)
+    return np.where(m > 0, 2.0 ** np.rint(np.log2(np.where(m > 0, m, 1.0))), 1.0)
+
+
+def _exact32(v64, what):
+    v32 = v64.astype(np.float32)
+    assert np.array_equal(v32.astype(np.float64), v64), f"{what}: {(v32.astype(np.float64) != v64).sum()} values are not exact in fp32"
+    return v32
+
+
+def exact_affine(rng, y):
+    """(adapter_scale, adapter_bias) per column of the exact y (M, N), float32 holding bf16 values: scale =
+    +-(odd integer) / 128 in [0.5, 1.5) (7 or 8 significant bits, never a power of two), bias = an integer in
+    [-255, 255] times mag_n / 128 (mag_n: the power of two nearest the column's mean |y|), of the size of y's
+    bf16 rounding step."""
+    N = np.asarray(y).shape[1]
+    scale = (2 * rng.integers(32, 96, size=N) + 1) / 128.0 * rng.choice([-1.0, 1.0], size=N)
+    bias = rng.integers(-255, 256, size=N) * _col_mag(y) / 128.0
+    scale, bias = scale.astype(np.float32), bias.astype(np.float32)
+    assert np.array_equal(bf16(scale), scale) and np.array_equal(bf16(bias), bias)
+    assert (np.abs(scale) >= 0.5).all() and (np.abs(scale) < 1.5).all()
+    return scale, bias
+
+
+def affine_bf16(y32, scale, bias, skip=None, parts=False):
+    """The adapter v2 epilogue bf16(bf16(bf16(y) + bias) * scale) (adapter_v2.py:28-31 on bf16 tensors) in
+    numpy float32. The fp32 sum and the fp32 product are asserted equal to their float64 values (no double
+    rounding). skip: "y" / "sum" = that rounding left out (the wrong-rounding variants; nothing asserted); any
+    other value, such as "none": every rounding kept, nothing asserted (vectors made for another y).
+    parts: also return the fp32 product before its rounding."""
+    y32 = np.asarray(y32, np.float32)
+    s64, b64 = scale.astype(np.float64)[None, :], bias.astype(np.float64)[None, :]
+    a = y32 if skip == "y" else bf16(y32)
+    s = a.astype(np.float64) + b64
+    s32 = _exact32(s, "affine sum") if skip is None else s.astype(np.float32)
+    t = s32 if skip == "sum" else bf16(s32)
+    p = t.astype(np.float64) * s64
+    p32 = _exact32(p, "affine product") if skip is None else p.astype(np.float32)
+    return (bf16(p32), p32) if parts else bf16(p32)
+
+
+LORA_SCALING = 0.75  # lora_alpha 6 / r 8: not a power of two
+
+
+def exact_lora(rng, y, M, r, n_en):
+    """(t, B) for the exact y (M, n_en Ng) of the enabled groups' columns, in group order: t (M, r n_en) integers
+    in [-8, 8]; B[n, j] (n_en Ng, r) = an integer in [-127, 127] times mag_n / 512. Every product is a multiple of
+    mag_n / 512 and |sum| <= 8 * 127 * 64 units < 2^24: d is exact in fp32 in any fmaf order for r <= 64."""
+    assert r <= 64 and np.asarray(y).shape == (M, np.asarray(y).shape[1]) and y.shape[1] % n_en == 0
+    t = rng.integers(-8, 9, size=(M, r * n_en)).astype(np.float32)
+    B = (rng.integers(-127, 128, size=(y.shape[1], r)) * (_col_mag(y) / 512.0)[:, None]).astype(np.float32)
+    assert np.array_equal(bf16(B), B)
+    return t, B
+
+
+def lora_delta(t, B, r, n_en):
+    """d[m, n] = sum_j t[m, g_i r + j] B[n, j] in float64 (exact), for the enabled groups' columns; asserted
+    exact in fp32."""
+    Ng = B.shape[0] // n_en
+    d = np.concatenate([t[:, gi * r:(gi + 1) * r].astype(np.float64) @ B[gi * Ng:(gi + 1) * Ng].astype(np.float64).T
+                        for gi in range(n_en)], 1)
+    _exact32(d, "LoRA d")
+    return d
+
+
+def lora_bf16(y32, d, scaling, enabled_cols, skip=None):
+    """The unmerged LoRA epilogue y = bf16(bf16(y) + bf16(bf16(d) * scaling)) on the columns `enabled_cols`
+    (lora.py:318-323 on bf16 tensors), bf16(y) elsewhere, in numpy float32; d (M, len(enabled_cols)) float64.
+    Product and sum are asserted exact in fp32. skip: "y" / "d" / "ds" = that rounding left out."""
+    y32 = np.asarray(y32, np.float32)
+    out = bf16(y32)
+    yb = (y32 if skip == "y" else out)[:, enabled_cols].astype(np.float64)
+    d32 = d.astype(np.float32)
+    db = d32 if skip == "d" else bf16(d32)
+    ds = db.astype(np.float64) * scaling
+    ds32 = _exact32(ds, "LoRA d * scaling") if skip is None else ds.astype(np.float32)
+    dsb = ds32 if skip == "ds" else bf16(ds32)
+    s = yb + dsb.astype(np.float64)
+    s32 = _exact32(s, "LoRA sum") if skip is None else s.astype(np.float32)
+    out = out.copy()
+    out[:, enabled_cols] = bf16(s32)
+    return out
+
+
+class RoundingPower:
+    """Test power over the cases of one test, from the references alone: the share of the pooled expected
+    elements in which each wrong-rounding variant differs from the right result (floor 10 %), and the share in
+    which the right result differs from the base expectation without the affine / the term (floor 99 %)."""
+
+    def __init__(self):
+        self.d, self.noop, self.extra = {}, [], {}
+
+    def require(self, name, arr, floor):
+        """A further input condition of the test: the mean of the pooled `arr` must exceed `floor`."""
+        self.extra.setdefault(name, ([], floor))[0].append(np.asarray(arr).ravel())
+
+    def extras(self):
+        return {k: (float(np.mean(np.concatenate(v))), fl) for k, (v, fl) in self.extra.items()}
+
+    def add(self, want, wrong, base=None, count=True):
+        """count False: the case adds to the no-op share only (a shape outside the pool, K < 640)."""
+        if count:
+            for k, v in wrong.items():
+                self.d.setdefault(k, []).append((np.asarray(v) != want).ravel())
+        if base is not None:
+            self.noop.append((np.asarray(base) != want).ravel())
+
+    def shares(self):
+        return {k: float(np.mean(np.concatenate(v))) for k, v in self.d.items()}
+
+    def changed(self):
+        return float(np.mean(np.concatenate(self.noop))) if self.noop else None
+
+    def ok(self, exempt=()):
+        ch = self.changed()
+        return (all(s >= 0.10 for k, s in self.shares().items() if k not in exempt) and (ch is None or ch >= 0.99)
+                and all(v > fl for v, fl in self.extras().values()))
+
+    def finish(self, what, exempt=(), seed=None):
+        s, ch = self.shares(), self.changed()
+        print(f"{what}: wrong-rounding shares " + ", ".join(f"{k} {v:.3f}" for k, v in s.items())
+              + (f"; exempt {tuple(exempt)}" if exempt else "") + (f"; differs from the base in {ch:.4f}" if ch is not None else "")
+              + "".join(f"; {k} {v:.3f}" for k, (v, fl) in self.extras().items())
+              + (f"; seed {seed}" if seed is not None else ""))
+        for k, (v, fl) in self.extras().items():
+            assert v > fl, f"{what}: {k} is {v:.4f}, not above {fl}"
+        for k, v in s.items():
+            assert k in exempt or v >= 0.10, f"{what}: variant {k} differs in only {v:.4f} of the elements"
+        assert ch is None or ch >= 0.99, f"{what}: the epilogue changes only {ch:.4f} of the elements"
+        return s
+
+
 # ------------------------------------------------------------------ exact LLM.int8 operands
 # Inputs for which the LLM.int8 kernels (wfmt 2) have one correct bit pattern (tests/test_int8_exact_gpu.py):
 # with SCA = 127 * 2^-j and SCB = 127 * 2^-e the fp32 dequantization constant SCA * SCB / 127^2 is exactly

@@ -19,7 +19,10 @@ those files compare the fused epilogues with kernels that are themselves checked
     llj_g_embedding   test_embedding_rows_and_pos_inc (and llj_embedding at C % 8 != 0)
     llj_g_sample      test_sample_fp32_vs_restatement
     (llj_g_i8_linear: tests/test_generic_gpu.py::test_generic_int8_linear_vs_oracle; llj_g_linear_v2 /
-    llj_g_linear_lora: the adapter v2 / LoRA kernel tests; llj_g_nll: tests/test_nll_kernels_gpu.py)
+    llj_g_linear_lora: bitwise against numpy on exact operands in tests/test_epilogue_exact_gpu.py
+    (test_g_linear_v2_exact, test_g_linear_lora_exact) -- the adapter v2 / LoRA kernel tests compare them with
+    llj_g_linear followed by torch arithmetic, which covers their argument rules and identity forms only;
+    llj_g_nll: tests/test_nll_kernels_gpu.py)
 
 dt = 0 is bf16 (inputs are bf16 values, outputs compared after the reference's rounding points), dt = 1
 fp32. Padding columns and untouched cache slots are pre-filled with a sentinel and compared too.

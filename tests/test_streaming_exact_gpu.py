@@ -438,9 +438,12 @@ QKV_G = (-4, -3, 3, 4)  # norm weights of the QKV cases: large enough that K = 1
 QKV_ROWS = [(1, 1, None), (8, 1, None), (8, 1, "hand"), (8, 0, "hand"), (1, 2, "hand"), (10, 1, None), (10, 1, "hand")]
 
 
-def qkv_expect(y, B, T_, nh, hs, S, pos, rope, q0=None, k0=None, v0=None):
+def qkv_expect(y, B, T_, nh, hs, S, pos, rope, q0=None, k0=None, v0=None, exact=True):
     """Expected q (B T, C) and caches (B, nh, S, hs) as float32 with NaN where the sentinel must stay, from
-    the exact c_attn output y (B T, 3 C); ring slot pos % S; the wrong-rounding variant rotates y itself."""
+    the exact c_attn output y (B T, 3 C); ring slot pos % S; the wrong-rounding variant rotates y itself.
+    exact False (tests/test_epilogue_exact_gpu.py): the rotation of partners of very different size need not fit
+    fp32; both products are exact in fp32 (8 x 4 significant bits), so the fp32 result is the one rounding of the
+    exact value however the two products are contracted, which is what rope_bf16 computes."""
     C, Mr = nh * hs, B * T_
     v = bf16(y.astype(f32))
     cs = rope[np.asarray(pos)][None, :, None]  # (1, T, 1, hs / 2, 2)
@@ -449,7 +452,7 @@ def qkv_expect(y, B, T_, nh, hs, S, pos, rope, q0=None, k0=None, v0=None):
         return [z[:, i * C:(i + 1) * C].reshape(B, T_, nh, hs) for i in range(3)]
 
     q, k, vv = split(v)
-    qe, ke = H.rope_bf16(q, cs), H.rope_bf16(k, cs)
+    qe, ke = H.rope_bf16(q, cs, exact), H.rope_bf16(k, cs, exact)
     qu, ku, _ = split(y)
     wrong_share = float(np.mean(np.concatenate([(H.rope_bf16(qu, cs, exact=False) != qe).ravel(),
                                                 (H.rope_bf16(ku, cs, exact=False) != ke).ravel()])))
