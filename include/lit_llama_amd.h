@@ -502,4 +502,8 @@ int llj_stream_read(const void* p, size_t bytes, float* out, int grid, void* str
  * share a prompt prefix) likewise. */
 #include "lit_llama_amd_samples.h"
 
+/* The entry point for decoding prompts of different lengths as one batch (llj_attention_ragged: RoPE, KV write
+ * and decode attention at a position per row) likewise. */
+#include "lit_llama_amd_ragged.h"
+
 #endif /* LIT_LLAMA_AMD_H */

@@ -9,6 +9,10 @@ top_k / temperatures in the device top-k sampler.
 `generate_samples()` (CLI: --batch_samples) produces the num_samples continuations of one prompt as one batch:
 one prefill, every row its own draws, one decode step for all rows (DecodeSession.prefill_shared).
 
+`generate_prompts()` (CLI: --prompts_file) continues several prompts of different lengths as one batch: each
+prompt prefilled as generate() does it, then one decode step for all rows, every row at its own position
+(DecodeSession.prefill_ragged).
+
 CLI flags follow reference generate.py:92-102 (argparse; jsonargparse is not installed).
 The default CLI decode (top_k=200, temperature=0.8) runs the same captured graph as greedy, with
 the device sampler (llj_sample) in place of the argmax.
@@ -133,12 +137,66 @@ def generate_samples(model: LLaMA, idx: torch.Tensor, num_samples: int, max_new_
     return rows
 
 
+@torch.no_grad()
+def generate_prompts(model: LLaMA, prompts, max_new_tokens: int, *, max_seq_length: Optional[int] = None,
+                     temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None) -> list:
+    """Continuations of several 1-D prompts of any lengths as one batch (DecodeSession.prefill_ragged): every
+    prompt is prefilled as generate() prefills it, then one decode step serves all rows, each at its own
+    position. Returns one 1-D tensor per prompt, in order, each cut by the reference's EOS rule (the EOS token
+    itself excluded); with eos_id the host looks at the ids every EOS_CHECK_EVERY steps and stops once every row
+    has one. Sampling draws row b's uniform at step position p from hash(seed, p, b), p the position shared by
+    the batch (the longest prompt's), the seed from torch's default generator as in generate().
+    max_seq_length defaults to min(Tmax + max_new_tokens, block_size), Tmax the longest prompt. The prompts run
+    one after the other through generate(), as before this function existed, when there is only one, when
+    model.ragged_support() names a reason (LLM.int8, unmerged LoRA, fp32 / any-shape models), or when
+    Tmax + max_new_tokens exceeds max_seq_length (the batch's caches do not wrap)."""
+    prompts = list(prompts)
+    if not prompts:
+        return []
+    lens = [int(p.size(0)) for p in prompts]
+    tmax = max(lens)
+    msl = min(tmax + max_new_tokens, model.config.block_size) if max_seq_length is None else max_seq_length
+    if len(prompts) == 1 or tmax + max_new_tokens > msl or model.ragged_support() is not None:
+        return [generate(model, p, max_new_tokens, max_seq_length=max_seq_length, temperature=temperature,
+                         top_k=top_k, eos_id=eos_id) for p in prompts]
+    if max_new_tokens <= 0:
+        return [p.clone() for p in prompts]
+    seed = 0 if top_k == 1 else int(torch.randint(0, 2 ** 62, (1,)))
+    sess = DecodeSession(model, len(prompts), msl, tmax + max_new_tokens, temperature=temperature, top_k=top_k,
+                         seed=seed)
+    sess.prefill_ragged(prompts)
+    left = max_new_tokens - 1
+    while left:
+        if eos_id is not None and bool((sess.output()[:, tmax:] == eos_id).any(dim=1).all()):
+            break
+        n = min(left, EOS_CHECK_EVERY) if eos_id is not None else left
+        sess.decode(n)
+        left -= n
+    rows = []
+    for row, p in zip(sess.output_rows(), prompts):
+        row = row.to(p.dtype)
+        if eos_id is not None:
+            hit = (row[p.size(0):] == eos_id).nonzero()
+            if hit.numel():
+                row = row[:p.size(0) + int(hit[0, 0])]
+        rows.append(row)
+    return rows
+
+
+def read_prompts_file(path) -> list:
+    """The prompts of --prompts_file: one per non-empty line, in file order."""
+    with open(path, encoding="utf-8") as f:
+        return [line.strip() for line in f if line.strip()]
+
+
 def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tokens: int = 50, top_k: int = 200,
          temperature: float = 0.8, checkpoint_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
-         batch_samples: bool = False) -> None:
+         batch_samples: bool = False, prompts_file: Optional[Path] = None) -> None:
     """Generates text samples based on a pre-trained LLaMA model and tokenizer (reference generate.py:92-155).
-    batch_samples: the num_samples samples as one batch (generate_samples) instead of one after the other."""
+    batch_samples: the num_samples samples as one batch (generate_samples) instead of one after the other.
+    prompts_file: one prompt per non-empty line instead of `prompt`, all generated as one batch
+    (generate_prompts), the texts printed in file order."""
     assert checkpoint_path.is_file(), checkpoint_path
     assert tokenizer_path.is_file(), tokenizer_path
     if not torch.cuda.is_available():
@@ -157,6 +215,22 @@ def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tok
     encoded = tokenizer.encode(prompt, bos=True, eos=False, device=torch.device("cuda"))
     prompt_length = encoded.size(0)
     torch.manual_seed(1234)
+    if prompts_file is not None:
+        dev = torch.device("cuda")
+        enc = [tokenizer.encode(text, bos=True, eos=False, device=dev) for text in read_prompts_file(prompts_file)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        model.reset_cache()
+        for y in ys:
+            print(tokenizer.decode(y))
+        tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, enc))
+        print(f"Time for inference of {len(enc)} prompts: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec",
+              file=sys.stderr)
+        print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+        return
     if batch_samples:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -196,7 +270,10 @@ if __name__ == "__main__":
     ap.add_argument("--quantize", default=None, choices=[None, "llm.int8", "gptq.int4", "gptq.int8"])
     ap.add_argument("--batch_samples", action="store_true",
                     help="generate the num_samples samples as one batch: the prompt is prefilled once")
+    ap.add_argument("--prompts_file", type=Path, default=None,
+                    help="a file with one prompt per non-empty line, replacing --prompt: all lines are generated as "
+                         "one batch, whatever their lengths, and printed in file order")
     a = ap.parse_args()
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_path=a.checkpoint_path, tokenizer_path=a.tokenizer_path,
-         quantize=a.quantize, batch_samples=a.batch_samples)
+         quantize=a.quantize, batch_samples=a.batch_samples, prompts_file=a.prompts_file)

@@ -20,7 +20,7 @@ import torch
 wd = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(wd))
 
-from generate import generate  # noqa: E402  (generate.py next to this directory)
+from generate import generate, generate_prompts, read_prompts_file  # noqa: E402  (generate.py next to this directory)
 from lit_llama import HFTokenizer, Tokenizer  # noqa: E402
 from lit_llama.adapter import LLaMA  # noqa: E402
 from lit_llama.checkpoint import read_checkpoint  # noqa: E402
@@ -47,8 +47,11 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
          adapter_path: Path = Path("out/adapter/alpaca/lit-llama-adapter-finetuned.pth"),
          pretrained_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
-         max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8) -> None:
-    """Generates a response to an instruction and an optional input (reference generate/adapter.py:21-94)."""
+         max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8,
+         prompts_file: Optional[Path] = None) -> None:
+    """Generates a response to an instruction and an optional input (reference generate/adapter.py:21-94).
+    prompts_file: one instruction per non-empty line instead of `prompt` / `input`, each wrapped in the Alpaca
+    prompt, all generated as one batch (generate.generate_prompts) and each response printed in file order."""
     assert adapter_path.is_file(), adapter_path
     assert pretrained_path.is_file(), pretrained_path
     assert tokenizer_path.is_file(), tokenizer_path
@@ -67,6 +70,24 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
     print(f"Time to load model: {time.time() - t0:.02f} seconds.", file=sys.stderr)
     model.eval()
     tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
+    if prompts_file is not None:
+        dev = torch.device("cuda")
+        enc = [tokenizer.encode(generate_prompt({"instruction": line, "input": ""}), bos=True, eos=False, device=dev)
+               for line in read_prompts_file(prompts_file)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k,
+                              eos_id=tokenizer.eos_id)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        model.reset_cache()
+        for y in ys:
+            print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
+        tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, enc))
+        print(f"\n\nTime for inference of {len(enc)} instructions: {t:.02f} sec total, "
+              f"{tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+        print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+        return
     text = generate_prompt({"instruction": prompt, "input": input})
     encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
     prompt_length = encoded.size(0)
@@ -93,6 +114,9 @@ if __name__ == "__main__":
     ap.add_argument("--max_new_tokens", type=int, default=100)
     ap.add_argument("--top_k", type=int, default=200)
     ap.add_argument("--temperature", type=float, default=0.8)
+    ap.add_argument("--prompts_file", type=Path, default=None,
+                    help="a file with one instruction per non-empty line, replacing --prompt / --input: all are "
+                         "generated as one batch and each response printed in file order")
     a = ap.parse_args()
     main(a.prompt, a.input, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
-         a.top_k, a.temperature)
+         a.top_k, a.temperature, a.prompts_file)

@@ -1,5 +1,5 @@
 """ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h and the
-lit_llama_amd_lora.h, lit_llama_amd_nll.h and lit_llama_amd_samples.h it includes).
+lit_llama_amd_lora.h, lit_llama_amd_nll.h, lit_llama_amd_samples.h and lit_llama_amd_ragged.h it includes).
 
 The library is the only compute path of this package: there is no CPU or eager-PyTorch
 fallback. If it is missing or the device is not a ROCm GPU, calls raise.
@@ -126,6 +126,13 @@ SAMPLES_SIGNATURES = {
     "llj_attention_shared": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
 }
 
+# the entry point for decoding prompts of different lengths as one batch (include/lit_llama_amd_ragged.h, which
+# lit_llama_amd.h includes): RoPE, KV write and decode attention at a position per row. A table of its own, as
+# the header is.
+RAGGED_SIGNATURES = {
+    "llj_attention_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -148,7 +155,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no fallback path.")
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, argt in {**SIGNATURES, **LORA_SIGNATURES, **NLL_SIGNATURES}.items():
+        for name, argt in {**SIGNATURES, **LORA_SIGNATURES, **NLL_SIGNATURES, **RAGGED_SIGNATURES}.items():
             f = getattr(L, name)
             f.argtypes = argt
             f.restype = ctypes.c_int

@@ -12,7 +12,10 @@ generate.py:86).
 
 Batch B > 1 decodes B equal-length prompts together (each row equals an independent B=1
 run: tests/test_model_gpu.py); the reference's generate() is batch 1 only (generate.py:62). Up to 8
-rows share every fused launch; larger batches take the ops in row slices.
+rows share every fused launch; larger batches take the ops in row slices. Prompts of different
+lengths decode together after prefill_ragged: the step position stays shared, each row's own position
+is pos - off[b], and c_attn's plain store + llj_attention_ragged replace the fused c_attn epilogue and
+the decode attention.
 """
 from __future__ import annotations
 
@@ -21,6 +24,33 @@ import torch
 from . import _hip
 from . import model as _model
 from .model import LLaMA, _Work
+
+
+def ragged_layout(lengths) -> tuple:
+    """(Tmax, off) of prompts of these lengths decoded as one batch (prefill_ragged): off[b] = Tmax - T_b, the
+    padding on the left of row b in the token buffer and the distance of row b's own position from the shared
+    step position."""
+    lengths = [int(t) for t in lengths]
+    if not lengths or min(lengths) < 1:
+        raise ValueError(f"every prompt needs at least one token, got lengths {lengths}")
+    tmax = max(lengths)
+    return tmax, [tmax - t for t in lengths]
+
+
+def left_padded(prompts, total_len: int, tokens: torch.Tensor | None = None) -> torch.Tensor:
+    """The (B, total_len) int32 token buffer of a ragged session: row b's prompt in columns off[b] .. Tmax - 1
+    (zeros on its left), so that every row's new tokens start at column Tmax. Fills `tokens` if given."""
+    tmax, off = ragged_layout([p.numel() for p in prompts])
+    if tokens is None:
+        tokens = torch.zeros(len(prompts), total_len, dtype=torch.int32, device=prompts[0].device)
+    for b, p in enumerate(prompts):
+        tokens[b, off[b]:tmax] = p.reshape(-1).to(device=tokens.device, dtype=torch.int32)
+    return tokens
+
+
+def rows_of(tokens: torch.Tensor, off, end: int) -> list:
+    """Row b of a left-padded token buffer without its padding: tokens[b, off[b]:end]."""
+    return [tokens[b, o:end] for b, o in enumerate(off)]
 
 
 class DecodeSession:
@@ -49,6 +79,8 @@ class DecodeSession:
         self.steps_done = 0
         self.specs = None
         self.work = None
+        self.off = None       # prefill_ragged: (B,) int32 on the device, row b stands at pos - off[b]
+        self.offsets = None   # ... and the same as a host list
         self.temperature = float(temperature)
         self.top_k = 0 if top_k is None else int(top_k)
         self.seed = int(seed) & ((1 << 64) - 1)
@@ -95,10 +127,17 @@ class DecodeSession:
         self.steps_done = 1
         self._setup_work()
 
-    def _setup_work(self, shared_prefix: int = 0) -> None:
-        """decode-step operands (fixed for the session); shared_prefix: see prefill_shared"""
+    def _setup_work(self, shared_prefix: int = 0, ragged: bool = False) -> None:
+        """decode-step operands (fixed for the session); shared_prefix: see prefill_shared; ragged: see
+        prefill_ragged (which has checked model.ragged_support())"""
         m, B = self.model, self.B
         self.specs = m._layer_specs()
+        if ragged:
+            self.work = _Work(m.config, B, self.dev, False, self.S, ragged=True)
+            self.work.off = self.off
+            self.graph = None
+            return
+        self.off = self.offsets = None
         if m._generic():  # the any-shape kernels (csrc/generic.hip)
             self.work = _Work(m.config, B, self.dev, False, self.S, generic=True, dtype=m.act_dtype(),
                               lora_cols=self.specs.get("lora_cols", 0))
@@ -148,6 +187,56 @@ class DecodeSession:
         self.steps_done = 1
         shared = T if (self.total <= self.S and T >= _model.SHARED_PREFIX_MIN) else 0
         self._setup_work(shared)
+
+    @torch.no_grad()
+    def prefill_ragged(self, prompts) -> None:
+        """prefill() for B prompts of different lengths (a list of 1-D tensors, T_b >= 1 tokens each) that then
+        decode as one batch. With Tmax = max T_b and off[b] = Tmax - T_b:
+          * row b is prefilled exactly as a B = 1 session prefills it, into row b of the caches (slot p holds
+            its token at its own position p) and row b of self.logits: bitwise a B = 1 session's;
+          * the token buffer is left-padded: row b's prompt in tokens[b, off[b]:Tmax], every row's new tokens
+            from column Tmax on (output_rows() drops the padding);
+          * the step position stays the one device int `pos` (Tmax - 1 after the prefill, advanced by the
+            embedding launch); row b's own position is pos - off[b], which only llj_attention_ragged needs
+            (RoPE angle, cache slot, key count). The samplers' counter hash (seed, pos, row) and a `uniforms`
+            table are indexed by the shared step position, not by the row's own.
+        The ring must not wrap: Tmax + 1 <= total_len <= S. Raises NotImplementedError with the reason where
+        model.ragged_support() gives one. t_prompt = Tmax, so decode()'s bounds hold unchanged."""
+        m, B = self.model, self.B
+        if len(prompts) != B:
+            raise ValueError(f"{len(prompts)} prompts for a session of batch {B}")
+        tmax, offsets = ragged_layout([p.numel() for p in prompts])
+        if not (tmax + 1 <= self.total <= self.S):
+            raise ValueError(f"the longest prompt ({tmax} tokens) and the new tokens must fit the cache without "
+                             f"wrapping: need {tmax} + 1 <= total_len ({self.total}) <= max_seq_length ({self.S})")
+        why = m.ragged_support()
+        if why is not None:
+            raise NotImplementedError(why)
+        m.reset_cache()
+        m.kv_caches = m._alloc_kv(B, self.S, self.dev)
+        if m.rope_cache is None:
+            m.rope_cache = m.build_rope_cache(prompts[0].to(self.dev))  # (the table lives where the idx does)
+        for b, p in enumerate(prompts):
+            T = p.numel()
+            pos = torch.arange(T, device=self.dev, dtype=torch.int32)
+            row = [(kc[b:b + 1], vc[b:b + 1]) for kc, vc in m.kv_caches]  # contiguous views: a one-row cache
+            m._run(p.reshape(1, -1).to(self.dev), pos, self.S, row, last_only_out=self.logits[b:b + 1])
+        st = _hip.stream()
+        self.tokens.zero_()
+        left_padded(prompts, self.total, self.tokens)
+        self.offsets = offsets
+        self.off = torch.tensor(offsets, dtype=torch.int32, device=self.dev)
+        self.pos.fill_(tmax - 1)
+        self._choose(st)
+        self.t_prompt = tmax
+        self.steps_done = 1
+        self._setup_work(ragged=True)
+
+    def output_rows(self) -> list:
+        """The rows of output() without the left padding of a ragged session: tokens[b, off[b] : t_prompt +
+        steps_done] (prompt and new tokens of row b); off = 0 after prefill / prefill_shared."""
+        off = self.offsets if self.offsets is not None else [0] * self.B
+        return rows_of(self.tokens, off, self.t_prompt + self.steps_done)
 
     def _reset_handoff(self):
         """The LLM.int8 hand-off blocks (_Work.y_st / h_st) must be zero when a step starts; a

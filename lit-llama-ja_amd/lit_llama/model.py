@@ -16,6 +16,9 @@ and ln_f + lm_head (llj_norm_linear). The KV cache is a ring: the token at absol
 position p is stored in slot p % S, which holds the same key set as the reference's
 roll-by-one sliding window (model.py:221-227); `kv_caches` therefore equals the reference's
 caches up to a rotation of the slot axis once more than S tokens were seen.
+Decode rows that each stand at a position of their own (prompts of different lengths in one batch,
+DecodeSession.prefill_ragged) replace 1 and 2 by llj_norm_linear into a qkv scratch and
+llj_attention_ragged (RoPE, KV write and attention at pos - off[b]); the ring does not wrap there.
 
 The model must live on a ROCm GPU, in bfloat16 (the reference's GPU precision, generate.py:121) or
 in float32 (the reference's CPU / evaluate/full.py default precision: every op then runs on the
@@ -335,9 +338,15 @@ class _Work:
     """Per-call scratch for M rows (allocated from torch's caching allocator)."""
 
     def __init__(self, cfg: LLaMAConfig, M: int, device, need_i8: bool, S: int = 0, gemm: bool = False,
-                 generic: bool = False, dtype=torch.bfloat16, lora_cols: int = 0, shared_prefix: int = 0):
+                 generic: bool = False, dtype=torch.bfloat16, lora_cols: int = 0, shared_prefix: int = 0,
+                 ragged: bool = False):
         C, H = cfg.n_embd, MLP.hidden(cfg)
         bf = torch.bfloat16
+        # decode rows at a position each (DecodeSession.prefill_ragged): c_attn stores into qkv and
+        # llj_attention_ragged does RoPE, the KV write and the attention; off (B int32, set by the session): row
+        # b stands at *pos - off[b]. Off by default.
+        self.ragged = False
+        self.off = None
         # decode rows whose caches share their first shared_prefix slots (DecodeSession.prefill_shared); 0: none
         self.shared_prefix = 0
         self.shared_ws = None
@@ -415,6 +424,9 @@ class _Work:
             self.shared_split = shared_splits(shared_prefix, cfg.n_head, M)
             nb = _hip.lib().llj_attention_shared_ws_bytes(M, cfg.n_head, C // cfg.n_head, self.shared_split)
             self.shared_ws = torch.empty(nb, dtype=torch.uint8, device=device)
+        if ragged and not gemm:
+            self.ragged = True
+            self.qkv = torch.empty(M, 3 * C, dtype=bf, device=device)
 
 
 class LLaMA(nn.Module):
@@ -686,6 +698,38 @@ class LLaMA(nn.Module):
         if ad is not None:
             self._prefix_add(ad, w, B * T, st)
 
+    def _attention_ragged(self, w, kc, vc, pos, B, S, st, i):
+        """RoPE, KV write and attention of B decode rows at a position each (row b at *pos - w.off[b]) from
+        c_attn's stored output w.qkv: one launch into w.q, slot p_b of the caches and w.y; on an adapter prefix
+        layer llj_adapter_prefix_add follows (it reads w.q)."""
+        cfg = self.config
+        C, nh = cfg.n_embd, cfg.n_head
+        rope = self.rope_cache
+        _hip.call("llj_attention_ragged", w.qkv.data_ptr(), w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                  w.y.data_ptr(), rope.data_ptr(), pos.data_ptr(), w.off.data_ptr(), B, nh, C // nh, S, rope.shape[0],
+                  st)
+        ad = self._adapter(i)
+        if ad is not None:
+            self._prefix_add(ad, w, B, st)
+
+    def ragged_support(self) -> Optional[str]:
+        """None if this model decodes rows at a position each (DecodeSession.prefill_ragged,
+        generate.generate_prompts), else why not. The route takes streaming-path models whose Linears are
+        bf16, gptq.int4, gptq.int8 or grouped int4: plain models, LLaMA-Adapter, adapter v2 and merged LoRA."""
+        if self._generic():
+            return ("the any-shape / fp32 models (csrc/generic.hip) have no decode route with a position per row: "
+                    f"{self.config.kernel_support() or 'float32 activations'}")
+        if ATT_MERGE > 1:
+            return "ATT_MERGE (attention partials merged in attn.c_proj) has no form with a position per row"
+        specs = self._layer_specs()
+        if any(s[0] == 2 for layer in specs["layers"] for s in layer) or specs["head"][0] == 2:
+            return ("LLM.int8 Linears (Linear8bitLt): their decode attention hands the int8 statistics of its output "
+                    "on, which the attention with a position per row does not")
+        if "lora" in specs:
+            return ("unmerged LoRA: the low-rank term lives in the fused c_attn epilogue, which the route with a "
+                    "position per row replaces by a plain store; merge the weights first")
+        return None
+
     def _gemm_ok(self, specs, M):
         cfg = self.config
         C, H = cfg.n_embd, MLP.hidden(cfg)
@@ -877,8 +921,15 @@ class LLaMA(nn.Module):
                 src, nw = w.x, blk.rms_1.scale.data_ptr()
             nst = w.nst if (w.hand and i > 0 and fa != 2) else None
             lo = specs["lora"][i] if "lora" in specs else None
+            ragged = w.ragged and T == 1  # rows at a position each: see _attention_ragged
             for r0 in range(0, M if src is not None else 0, QKV_ROWS):
                 r = min(QKV_ROWS, M - r0)
+                if ragged:  # c_attn of the same rows and operands with the plain-store epilogue
+                    _lcall("llj_norm_linear", aa, fa, src[r0].data_ptr(), nw, blk.rms_1.eps, wa.data_ptr(), P(sa),
+                           w.qkv[r0].data_ptr(), w.qkv.stride(0), r, 3 * C, C, P(w.i8ws), r0,
+                           None if rs is None else rs[r0].data_ptr(), None if nst is None else nst[r0].data_ptr(),
+                           w.npart, st)
+                    continue
                 if lo is not None:
                     # unmerged LoRA: t = rms_1(x) . lora_A^T as a small dense Linear on the same rows (and the
                     # same norm hand-off), then c_attn with the low-rank term in its epilogue
@@ -906,6 +957,9 @@ class LLaMA(nn.Module):
                           C // nh, S, w.att_merge, w.att_part.data_ptr(), st)
                 _lcall("llj_linear_resid_attn", ap, fp, w.att_part.data_ptr(), w.att_merge, nh, wp.data_ptr(), P(sp),
                        w.x.data_ptr(), C, C, C, P(w.nst) if w.hand else None, st)
+            elif ragged:
+                self._attention_ragged(w, kc, vc, pos, B, S, st, i)
+                self._resid(fp, w.y, wp, sp, w.x, M, C, C, w, st, w.nst if w.hand else None, ap)
             else:
                 self._attention(w, kc, vc, pos, B, T, S, st, i)
                 self._resid(fp, w.y, wp, sp, w.x, M, C, C, w, st, w.nst if w.hand else None, ap)
