@@ -506,4 +506,8 @@ int llj_stream_read(const void* p, size_t bytes, float* out, int grid, void* str
  * and decode attention at a position per row) likewise. */
 #include "lit_llama_amd_ragged.h"
 
+/* The entry points for prefilling prompts of different lengths as one packed batch (llj_rope_kv_packed,
+ * llj_attention_prefill_packed) likewise. */
+#include "lit_llama_amd_packed.h"
+
 #endif /* LIT_LLAMA_AMD_H */

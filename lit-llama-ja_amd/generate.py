@@ -11,7 +11,8 @@ one prefill, every row its own draws, one decode step for all rows (DecodeSessio
 
 `generate_prompts()` (CLI: --prompts_file) continues several prompts of different lengths as one batch: each
 prompt prefilled as generate() does it, then one decode step for all rows, every row at its own position
-(DecodeSession.prefill_ragged).
+(DecodeSession.prefill_ragged). With packed_prefill=True (CLI: --packed_prefill) the prompts are also prefilled
+as one batch of packed rows, every Linear's weights streamed once instead of once per prompt.
 
 CLI flags follow reference generate.py:92-102 (argparse; jsonargparse is not installed).
 The default CLI decode (top_k=200, temperature=0.8) runs the same captured graph as greedy, with
@@ -139,7 +140,8 @@ def generate_samples(model: LLaMA, idx: torch.Tensor, num_samples: int, max_new_
 
 @torch.no_grad()
 def generate_prompts(model: LLaMA, prompts, max_new_tokens: int, *, max_seq_length: Optional[int] = None,
-                     temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None) -> list:
+                     temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None,
+                     packed_prefill: bool = False) -> list:
     """Continuations of several 1-D prompts of any lengths as one batch (DecodeSession.prefill_ragged): every
     prompt is prefilled as generate() prefills it, then one decode step serves all rows, each at its own
     position. Returns one 1-D tensor per prompt, in order, each cut by the reference's EOS rule (the EOS token
@@ -149,7 +151,11 @@ def generate_prompts(model: LLaMA, prompts, max_new_tokens: int, *, max_seq_leng
     max_seq_length defaults to min(Tmax + max_new_tokens, block_size), Tmax the longest prompt. The prompts run
     one after the other through generate(), as before this function existed, when there is only one, when
     model.ragged_support() names a reason (LLM.int8, unmerged LoRA, fp32 / any-shape models), or when
-    Tmax + max_new_tokens exceeds max_seq_length (the batch's caches do not wrap)."""
+    Tmax + max_new_tokens exceeds max_seq_length (the batch's caches do not wrap).
+    packed_prefill: the batch's prompts are prefilled as one run over their sum T_b packed rows instead of one
+    after the other (DecodeSession.prefill_ragged(packed=True); the per-prompt loop where
+    model.packed_prefill_support() names a reason, fewer than 32 tokens in all among them). The two prefills agree
+    to rounding, not bitwise."""
     prompts = list(prompts)
     if not prompts:
         return []
@@ -164,7 +170,7 @@ def generate_prompts(model: LLaMA, prompts, max_new_tokens: int, *, max_seq_leng
     seed = 0 if top_k == 1 else int(torch.randint(0, 2 ** 62, (1,)))
     sess = DecodeSession(model, len(prompts), msl, tmax + max_new_tokens, temperature=temperature, top_k=top_k,
                          seed=seed)
-    sess.prefill_ragged(prompts)
+    sess.prefill_ragged(prompts, packed=packed_prefill)
     left = max_new_tokens - 1
     while left:
         if eos_id is not None and bool((sess.output()[:, tmax:] == eos_id).any(dim=1).all()):
@@ -192,11 +198,12 @@ def read_prompts_file(path) -> list:
 def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tokens: int = 50, top_k: int = 200,
          temperature: float = 0.8, checkpoint_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
-         batch_samples: bool = False, prompts_file: Optional[Path] = None) -> None:
+         batch_samples: bool = False, prompts_file: Optional[Path] = None, packed_prefill: bool = False) -> None:
     """Generates text samples based on a pre-trained LLaMA model and tokenizer (reference generate.py:92-155).
     batch_samples: the num_samples samples as one batch (generate_samples) instead of one after the other.
     prompts_file: one prompt per non-empty line instead of `prompt`, all generated as one batch
-    (generate_prompts), the texts printed in file order."""
+    (generate_prompts), the texts printed in file order; packed_prefill: their prompts prefilled as one packed
+    batch as well (it means nothing without prompts_file)."""
     assert checkpoint_path.is_file(), checkpoint_path
     assert tokenizer_path.is_file(), tokenizer_path
     if not torch.cuda.is_available():
@@ -220,7 +227,8 @@ def main(prompt: str = "Hello, my name is", *, num_samples: int = 1, max_new_tok
         enc = [tokenizer.encode(text, bos=True, eos=False, device=dev) for text in read_prompts_file(prompts_file)]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k)
+        ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k,
+                              packed_prefill=packed_prefill)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         model.reset_cache()
@@ -273,7 +281,11 @@ if __name__ == "__main__":
     ap.add_argument("--prompts_file", type=Path, default=None,
                     help="a file with one prompt per non-empty line, replacing --prompt: all lines are generated as "
                          "one batch, whatever their lengths, and printed in file order")
+    ap.add_argument("--packed_prefill", action="store_true",
+                    help="with --prompts_file: prefill all prompts as one packed batch, every weight streamed once, "
+                         "instead of one prompt after the other")
     a = ap.parse_args()
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_path=a.checkpoint_path, tokenizer_path=a.tokenizer_path,
-         quantize=a.quantize, batch_samples=a.batch_samples, prompts_file=a.prompts_file)
+         quantize=a.quantize, batch_samples=a.batch_samples, prompts_file=a.prompts_file,
+         packed_prefill=a.packed_prefill)

@@ -43,15 +43,39 @@ def generate_prompt(example: dict) -> str:
     return "\n\n".join(sections)
 
 
+def run_prompts_file(model, tokenizer, prompts_file: Path, max_new_tokens: int, top_k: int, temperature: float,
+                     packed_prefill: bool = False) -> None:
+    """--prompts_file of the instruction CLIs (this one, generate/adapter_v2.py, generate/lora.py): every non-empty
+    line as an instruction in the Alpaca prompt, all generated as one batch (generate.generate_prompts, which runs
+    them one after the other where the model has no batched route), each response printed in file order."""
+    dev = torch.device("cuda")
+    enc = [tokenizer.encode(generate_prompt({"instruction": line, "input": ""}), bos=True, eos=False, device=dev)
+           for line in read_prompts_file(prompts_file)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k,
+                          eos_id=tokenizer.eos_id, packed_prefill=packed_prefill)
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    model.reset_cache()
+    for y in ys:
+        print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
+    tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, enc))
+    print(f"\n\nTime for inference of {len(enc)} instructions: {t:.02f} sec total, "
+          f"{tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+
+
 def main(prompt: str = "What food do lamas eat?", input: str = "",
          adapter_path: Path = Path("out/adapter/alpaca/lit-llama-adapter-finetuned.pth"),
          pretrained_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
          max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8,
-         prompts_file: Optional[Path] = None) -> None:
+         prompts_file: Optional[Path] = None, packed_prefill: bool = False) -> None:
     """Generates a response to an instruction and an optional input (reference generate/adapter.py:21-94).
     prompts_file: one instruction per non-empty line instead of `prompt` / `input`, each wrapped in the Alpaca
-    prompt, all generated as one batch (generate.generate_prompts) and each response printed in file order."""
+    prompt, all generated as one batch (generate.generate_prompts) and each response printed in file order;
+    packed_prefill: their prompts prefilled as one packed batch as well (it means nothing without prompts_file)."""
     assert adapter_path.is_file(), adapter_path
     assert pretrained_path.is_file(), pretrained_path
     assert tokenizer_path.is_file(), tokenizer_path
@@ -71,22 +95,7 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
     model.eval()
     tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
     if prompts_file is not None:
-        dev = torch.device("cuda")
-        enc = [tokenizer.encode(generate_prompt({"instruction": line, "input": ""}), bos=True, eos=False, device=dev)
-               for line in read_prompts_file(prompts_file)]
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        ys = generate_prompts(model, enc, max_new_tokens, temperature=temperature, top_k=top_k,
-                              eos_id=tokenizer.eos_id)
-        torch.cuda.synchronize()
-        t = time.perf_counter() - t0
-        model.reset_cache()
-        for y in ys:
-            print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
-        tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, enc))
-        print(f"\n\nTime for inference of {len(enc)} instructions: {t:.02f} sec total, "
-              f"{tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
-        print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+        run_prompts_file(model, tokenizer, prompts_file, max_new_tokens, top_k, temperature, packed_prefill)
         return
     text = generate_prompt({"instruction": prompt, "input": input})
     encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
@@ -117,6 +126,9 @@ if __name__ == "__main__":
     ap.add_argument("--prompts_file", type=Path, default=None,
                     help="a file with one instruction per non-empty line, replacing --prompt / --input: all are "
                          "generated as one batch and each response printed in file order")
+    ap.add_argument("--packed_prefill", action="store_true",
+                    help="with --prompts_file: prefill all prompts as one packed batch, every weight streamed once, "
+                         "instead of one prompt after the other")
     a = ap.parse_args()
     main(a.prompt, a.input, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
-         a.top_k, a.temperature, a.prompts_file)
+         a.top_k, a.temperature, a.prompts_file, a.packed_prefill)

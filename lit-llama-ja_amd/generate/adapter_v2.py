@@ -51,6 +51,37 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
          max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8) -> None:
     """Generates a response to an instruction and an optional input (reference generate/adapter_v2.py:22-96)."""
+    model, tokenizer = load(adapter_path, pretrained_path, tokenizer_path, quantize)
+    text = generate_prompt({"instruction": prompt, "input": input})
+    encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
+    prompt_length = encoded.size(0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    y = generate(model, encoded, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=tokenizer.eos_id)
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    model.reset_cache()
+    print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
+    tokens_generated = y.size(0) - prompt_length
+    print(f"\n\nTime for inference: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+
+
+def main_prompts_file(prompts_file: Path,
+                      adapter_path: Path = Path("out/adapter_v2/alpaca/lit-llama-adapter-finetuned.pth"),
+                      pretrained_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
+                      tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"),
+                      quantize: Optional[str] = None, max_new_tokens: int = 100, top_k: int = 200,
+                      temperature: float = 0.8, packed_prefill: bool = False) -> None:
+    """--prompts_file (main keeps the reference's signature): one instruction per non-empty line instead of --prompt /
+    --input, all generated as one batch as generate/adapter.py does it; packed_prefill: prefilled as one packed batch
+    as well."""
+    model, tokenizer = load(adapter_path, pretrained_path, tokenizer_path, quantize)
+    _V1.run_prompts_file(model, tokenizer, prompts_file, max_new_tokens, top_k, temperature, packed_prefill)
+
+
+def load(adapter_path: Path, pretrained_path: Path, tokenizer_path: Path, quantize: Optional[str]):
+    """(model, tokenizer) of the two checkpoints, on the GPU in eval mode."""
     assert adapter_path.is_file(), adapter_path
     assert pretrained_path.is_file(), pretrained_path
     assert tokenizer_path.is_file(), tokenizer_path
@@ -73,19 +104,7 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
     print(f"Time to load model: {time.time() - t0:.02f} seconds.", file=sys.stderr)
     model.eval()
     tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
-    text = generate_prompt({"instruction": prompt, "input": input})
-    encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
-    prompt_length = encoded.size(0)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    y = generate(model, encoded, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=tokenizer.eos_id)
-    torch.cuda.synchronize()
-    t = time.perf_counter() - t0
-    model.reset_cache()
-    print(tokenizer.decode(y).split(RESPONSE_MARK)[1].strip())
-    tokens_generated = y.size(0) - prompt_length
-    print(f"\n\nTime for inference: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
-    print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
+    return model, tokenizer
 
 
 if __name__ == "__main__":
@@ -99,6 +118,16 @@ if __name__ == "__main__":
     ap.add_argument("--max_new_tokens", type=int, default=100)
     ap.add_argument("--top_k", type=int, default=200)
     ap.add_argument("--temperature", type=float, default=0.8)
+    ap.add_argument("--prompts_file", type=Path, default=None,
+                    help="a file with one instruction per non-empty line, replacing --prompt / --input: all are "
+                         "generated as one batch and each response printed in file order")
+    ap.add_argument("--packed_prefill", action="store_true",
+                    help="with --prompts_file: prefill all prompts as one packed batch, every weight streamed once, "
+                         "instead of one prompt after the other")
     a = ap.parse_args()
-    main(a.prompt, a.input, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
-         a.top_k, a.temperature)
+    if a.prompts_file is not None:
+        main_prompts_file(a.prompts_file, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize,
+                          a.max_new_tokens, a.top_k, a.temperature, a.packed_prefill)
+    else:
+        main(a.prompt, a.input, a.adapter_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
+             a.top_k, a.temperature)

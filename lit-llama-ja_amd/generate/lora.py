@@ -74,19 +74,7 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
          tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"), quantize: Optional[str] = None,
          max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8) -> None:
     """Generates a response to an instruction and an optional input (reference generate/lora.py:25-106)."""
-    assert lora_path.is_file(), lora_path
-    assert pretrained_path.is_file(), pretrained_path
-    assert tokenizer_path.is_file(), tokenizer_path
-    if quantize == "llm.int8":
-        raise NotImplementedError("LoRA on LLM.int8 Linears is not supported (use no quantization, gptq.int4 or "
-                                  "gptq.int8)")
-    if not torch.cuda.is_available():
-        raise SystemExit("generate/lora.py runs on a ROCm GPU (MI355X) only")
-    print("Loading model ...", file=sys.stderr)
-    t0 = time.time()
-    model = load_model(read_checkpoint(pretrained_path), read_checkpoint(lora_path), quantize)
-    print(f"Time to load model: {time.time() - t0:.02f} seconds.", file=sys.stderr)
-    tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
+    model, tokenizer = load(lora_path, pretrained_path, tokenizer_path, quantize)
     text = generate_prompt({"instruction": prompt, "input": input})
     encoded = tokenizer.encode(text, bos=True, eos=False, device=torch.device("cuda"))
     prompt_length = encoded.size(0)
@@ -102,6 +90,37 @@ def main(prompt: str = "What food do lamas eat?", input: str = "",
     print(f"Memory used: {torch.cuda.max_memory_reserved() / 1e9:.02f} GB", file=sys.stderr)
 
 
+def main_prompts_file(prompts_file: Path, lora_path: Path = Path("out/lora/alpaca/lit-llama-lora-finetuned.pth"),
+                      pretrained_path: Path = Path("checkpoints/lit-llama/7B/lit-llama.pth"),
+                      tokenizer_path: Path = Path("checkpoints/lit-llama/tokenizer.model"),
+                      quantize: Optional[str] = None, max_new_tokens: int = 100, top_k: int = 200,
+                      temperature: float = 0.8, packed_prefill: bool = False) -> None:
+    """--prompts_file (main keeps the reference's signature): one instruction per non-empty line instead of --prompt /
+    --input, all generated as one batch as generate/adapter.py does it; packed_prefill: prefilled as one packed batch
+    as well. An unmerged LoRA on a quantized base has no batched route: generate_prompts runs its prompts one after
+    the other."""
+    model, tokenizer = load(lora_path, pretrained_path, tokenizer_path, quantize)
+    _V1.run_prompts_file(model, tokenizer, prompts_file, max_new_tokens, top_k, temperature, packed_prefill)
+
+
+def load(lora_path: Path, pretrained_path: Path, tokenizer_path: Path, quantize: Optional[str]):
+    """(model, tokenizer) of the two checkpoints (load_model), on the GPU in eval mode."""
+    assert lora_path.is_file(), lora_path
+    assert pretrained_path.is_file(), pretrained_path
+    assert tokenizer_path.is_file(), tokenizer_path
+    if quantize == "llm.int8":
+        raise NotImplementedError("LoRA on LLM.int8 Linears is not supported (use no quantization, gptq.int4 or "
+                                  "gptq.int8)")
+    if not torch.cuda.is_available():
+        raise SystemExit("generate/lora.py runs on a ROCm GPU (MI355X) only")
+    print("Loading model ...", file=sys.stderr)
+    t0 = time.time()
+    model = load_model(read_checkpoint(pretrained_path), read_checkpoint(lora_path), quantize)
+    print(f"Time to load model: {time.time() - t0:.02f} seconds.", file=sys.stderr)
+    tokenizer = HFTokenizer(tokenizer_path) if tokenizer_path.suffix == ".json" else Tokenizer(tokenizer_path)
+    return model, tokenizer
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Generates a response to an instruction with a LoRA fine-tuned model.")
     ap.add_argument("--prompt", default="What food do lamas eat?", help="the instruction (Alpaca style)")
@@ -113,6 +132,16 @@ if __name__ == "__main__":
     ap.add_argument("--max_new_tokens", type=int, default=100)
     ap.add_argument("--top_k", type=int, default=200)
     ap.add_argument("--temperature", type=float, default=0.8)
+    ap.add_argument("--prompts_file", type=Path, default=None,
+                    help="a file with one instruction per non-empty line, replacing --prompt / --input: all are "
+                         "generated as one batch and each response printed in file order")
+    ap.add_argument("--packed_prefill", action="store_true",
+                    help="with --prompts_file: prefill all prompts as one packed batch, every weight streamed once, "
+                         "instead of one prompt after the other")
     a = ap.parse_args()
-    main(a.prompt, a.input, a.lora_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
-         a.top_k, a.temperature)
+    if a.prompts_file is not None:
+        main_prompts_file(a.prompts_file, a.lora_path, a.pretrained_path, a.tokenizer_path, a.quantize,
+                          a.max_new_tokens, a.top_k, a.temperature, a.packed_prefill)
+    else:
+        main(a.prompt, a.input, a.lora_path, a.pretrained_path, a.tokenizer_path, a.quantize, a.max_new_tokens,
+             a.top_k, a.temperature)

@@ -1,5 +1,6 @@
 """ctypes binding of the in-tree HIP library `_lljamd.so` (C ABI: include/lit_llama_amd.h and the
-lit_llama_amd_lora.h, lit_llama_amd_nll.h, lit_llama_amd_samples.h and lit_llama_amd_ragged.h it includes).
+lit_llama_amd_lora.h, lit_llama_amd_nll.h, lit_llama_amd_samples.h, lit_llama_amd_ragged.h and
+lit_llama_amd_packed.h it includes).
 
 The library is the only compute path of this package: there is no CPU or eager-PyTorch
 fallback. If it is missing or the device is not a ROCm GPU, calls raise.
@@ -133,6 +134,14 @@ RAGGED_SIGNATURES = {
     "llj_attention_ragged": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
+# the entry points for prefilling prompts of different lengths as one packed batch (include/lit_llama_amd_packed.h,
+# which lit_llama_amd.h includes): RoPE + KV write and the flash attention over packed rows. A table of its own, as
+# the header is.
+PACKED_SIGNATURES = {
+    "llj_rope_kv_packed": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "llj_attention_prefill_packed": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -155,7 +164,8 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no fallback path.")
         L = ctypes.CDLL(str(LIB_PATH))
-        for name, argt in {**SIGNATURES, **LORA_SIGNATURES, **NLL_SIGNATURES, **RAGGED_SIGNATURES}.items():
+        for name, argt in {**SIGNATURES, **LORA_SIGNATURES, **NLL_SIGNATURES, **RAGGED_SIGNATURES,
+                           **PACKED_SIGNATURES}.items():
             f = getattr(L, name)
             f.argtypes = argt
             f.restype = ctypes.c_int

@@ -15,7 +15,8 @@ run: tests/test_model_gpu.py); the reference's generate() is batch 1 only (gener
 rows share every fused launch; larger batches take the ops in row slices. Prompts of different
 lengths decode together after prefill_ragged: the step position stays shared, each row's own position
 is pos - off[b], and c_attn's plain store + llj_attention_ragged replace the fused c_attn epilogue and
-the decode attention.
+the decode attention. prefill_ragged(packed=True) also prefills them as one batch of packed
+rows.
 """
 from __future__ import annotations
 
@@ -35,6 +36,26 @@ def ragged_layout(lengths) -> tuple:
         raise ValueError(f"every prompt needs at least one token, got lengths {lengths}")
     tmax = max(lengths)
     return tmax, [tmax - t for t in lengths]
+
+
+PACKED_QUERIES = 64  # queries per workgroup of llj_attention_prefill_packed
+
+
+def packed_layout(lengths) -> tuple:
+    """(cu, tiles) of prompts of these lengths prefilled as one packed batch (prefill_ragged(packed=True)): cu[b] is
+    the first of prompt b's rows in the M = cu[B] packed rows; tiles lists every (b, qb), the 64-query block qb of
+    prompt b, by descending key count min(T_b, 64 qb + 64) -- the causal attention's work per block, so the long
+    blocks start first -- with ties in (b, qb) order."""
+    lengths = [int(t) for t in lengths]
+    if not lengths or min(lengths) < 1:
+        raise ValueError(f"every prompt needs at least one token, got lengths {lengths}")
+    cu = [0]
+    for t in lengths:
+        cu.append(cu[-1] + t)
+    Q = PACKED_QUERIES
+    tiles = [(b, qb) for b, t in enumerate(lengths) for qb in range((t + Q - 1) // Q)]
+    tiles.sort(key=lambda bq: (-min(lengths[bq[0]], Q * bq[1] + Q), bq))
+    return cu, tiles
 
 
 def left_padded(prompts, total_len: int, tokens: torch.Tensor | None = None) -> torch.Tensor:
@@ -79,6 +100,7 @@ class DecodeSession:
         self.steps_done = 0
         self.specs = None
         self.work = None
+        self.packed_prefill = False  # prefill_ragged(packed=True) ran the prompts as one packed batch
         self.off = None       # prefill_ragged: (B,) int32 on the device, row b stands at pos - off[b]
         self.offsets = None   # ... and the same as a host list
         self.temperature = float(temperature)
@@ -189,7 +211,7 @@ class DecodeSession:
         self._setup_work(shared)
 
     @torch.no_grad()
-    def prefill_ragged(self, prompts) -> None:
+    def prefill_ragged(self, prompts, packed: bool = False) -> None:
         """prefill() for B prompts of different lengths (a list of 1-D tensors, T_b >= 1 tokens each) that then
         decode as one batch. With Tmax = max T_b and off[b] = Tmax - T_b:
           * row b is prefilled exactly as a B = 1 session prefills it, into row b of the caches (slot p holds
@@ -201,7 +223,12 @@ class DecodeSession:
             (RoPE angle, cache slot, key count). The samplers' counter hash (seed, pos, row) and a `uniforms`
             table are indexed by the shared step position, not by the row's own.
         The ring must not wrap: Tmax + 1 <= total_len <= S. Raises NotImplementedError with the reason where
-        model.ragged_support() gives one. t_prompt = Tmax, so decode()'s bounds hold unchanged."""
+        model.ragged_support() gives one. t_prompt = Tmax, so decode()'s bounds hold unchanged.
+        packed=True: the B prompts are prefilled as one batch of M = sum T_b packed rows (LLaMA._run_packed: every
+        Linear streams its weights once instead of B times) where model.packed_prefill_support(M) gives no reason,
+        and one after the other as above where it does. The packed rows run other GEMM kernels than a T_b-row
+        prefill, so its logits and K / V agree with the loop's to a tolerance, not bitwise. self.packed_prefill
+        records which route ran."""
         m, B = self.model, self.B
         if len(prompts) != B:
             raise ValueError(f"{len(prompts)} prompts for a session of batch {B}")
@@ -216,11 +243,15 @@ class DecodeSession:
         m.kv_caches = m._alloc_kv(B, self.S, self.dev)
         if m.rope_cache is None:
             m.rope_cache = m.build_rope_cache(prompts[0].to(self.dev))  # (the table lives where the idx does)
-        for b, p in enumerate(prompts):
-            T = p.numel()
-            pos = torch.arange(T, device=self.dev, dtype=torch.int32)
-            row = [(kc[b:b + 1], vc[b:b + 1]) for kc, vc in m.kv_caches]  # contiguous views: a one-row cache
-            m._run(p.reshape(1, -1).to(self.dev), pos, self.S, row, last_only_out=self.logits[b:b + 1])
+        self.packed_prefill = bool(packed) and m.packed_prefill_support(sum(p.numel() for p in prompts)) is None
+        if self.packed_prefill:
+            m._run_packed([p.to(self.dev) for p in prompts], self.S, m.kv_caches, self.logits)
+        else:
+            for b, p in enumerate(prompts):
+                T = p.numel()
+                pos = torch.arange(T, device=self.dev, dtype=torch.int32)
+                row = [(kc[b:b + 1], vc[b:b + 1]) for kc, vc in m.kv_caches]  # contiguous views: a one-row cache
+                m._run(p.reshape(1, -1).to(self.dev), pos, self.S, row, last_only_out=self.logits[b:b + 1])
         st = _hip.stream()
         self.tokens.zero_()
         left_padded(prompts, self.total, self.tokens)

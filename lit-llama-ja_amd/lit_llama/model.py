@@ -19,6 +19,9 @@ caches up to a rotation of the slot axis once more than S tokens were seen.
 Decode rows that each stand at a position of their own (prompts of different lengths in one batch,
 DecodeSession.prefill_ragged) replace 1 and 2 by llj_norm_linear into a qkv scratch and
 llj_attention_ragged (RoPE, KV write and attention at pos - off[b]); the ring does not wrap there.
+Prompts of different lengths prefilled as one batch of packed rows (LLaMA._run_packed, opt-in) run the
+prefill GEMMs over all rows with llj_gemm_linear + llj_rope_kv_packed for c_attn's fused epilogue and
+llj_attention_prefill_packed for the attention.
 
 The model must live on a ROCm GPU, in bfloat16 (the reference's GPU precision, generate.py:121) or
 in float32 (the reference's CPU / evaluate/full.py default precision: every op then runs on the
@@ -347,6 +350,10 @@ class _Work:
         # b stands at *pos - off[b]. Off by default.
         self.ragged = False
         self.off = None
+        # prompt rows of B sequences of different lengths packed into the M rows (LLaMA._run_packed sets it: an
+        # object with cu, tiles, n_tiles, B): c_attn stores into qkv, llj_rope_kv_packed and
+        # llj_attention_prefill_packed find each row's sequence and position through cu. Off by default.
+        self.packed = None
         # decode rows whose caches share their first shared_prefix slots (DecodeSession.prefill_shared); 0: none
         self.shared_prefix = 0
         self.shared_ws = None
@@ -712,6 +719,64 @@ class LLaMA(nn.Module):
         if ad is not None:
             self._prefix_add(ad, w, B, st)
 
+    def _attention_packed(self, w, kc, vc, M, S, st, i):
+        """Causal attention of M packed prompt rows (w.packed) into w.y, each row over its own sequence's cache row;
+        on an adapter prefix layer llj_adapter_prefix_add follows (it reads w.q)."""
+        cfg = self.config
+        C, nh = cfg.n_embd, cfg.n_head
+        pk = w.packed
+        _hip.call("llj_attention_prefill_packed", w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), w.y.data_ptr(),
+                  pk.cu.data_ptr(), pk.tiles.data_ptr(), pk.n_tiles, pk.B, M, nh, C // nh, S, st)
+        ad = self._adapter(i)
+        if ad is not None:
+            self._prefix_add(ad, w, M, st)
+
+    def packed_prefill_support(self, M: int) -> Optional[str]:
+        """None if this model prefills prompts of different lengths as one batch of M packed rows (_run_packed,
+        DecodeSession.prefill_ragged(packed=True)), else why not: ragged_support()'s reason, or fewer rows than
+        the prefill GEMMs take / a weight format without one."""
+        why = self.ragged_support()
+        if why is not None:
+            return why
+        if not self._gemm_ok(self._layer_specs(), M):
+            return (f"{M} packed rows do not run the prefill GEMMs (at least {GEMM_MIN_ROWS} rows, every Linear in a "
+                    "format with a prefill GEMM, n_embd and the MLP width multiples of 128)")
+        return None
+
+    @torch.no_grad()
+    def _run_packed(self, prompts, S, kv, last_only_out):
+        """_run for B prompts of different lengths (1-D token tensors, T_b >= 1) as M = sum T_b packed rows: row
+        cu[b] + t is token t of prompt b, at position t, written to slot t of row b of the caches kv (B, n_head, S,
+        head_size; T_b <= S). The layer loop is _blocks_gemm's over all M rows at once, with c_attn's plain store +
+        llj_rope_kv_packed for the fused QKV epilogue and llj_attention_prefill_packed for the attention; the
+        logits of each prompt's last token go into last_only_out (B, V). The caller has checked
+        packed_prefill_support(M)."""
+        from .engine import packed_layout
+
+        cfg = self.config
+        lengths = [int(p.numel()) for p in prompts]
+        cu, tiles = packed_layout(lengths)
+        B, M = len(lengths), cu[-1]
+        if max(lengths) > S:
+            raise ValueError(f"a prompt of {max(lengths)} tokens does not fit a cache of {S} slots")
+        specs = self._layer_specs()
+        if not self._gemm_ok(specs, M):  # (no GEMV form of the packed route: an error, not another path)
+            raise NotImplementedError(self.packed_prefill_support(M))
+        ids = torch.cat([p.reshape(-1) for p in prompts]).to(torch.int32)
+        dev = ids.device
+        w = _Work(cfg, M, dev, False, S, gemm=True)
+        w.qkv = torch.empty(M, 3 * cfg.n_embd, dtype=torch.bfloat16, device=dev)
+        w.packed = types.SimpleNamespace(
+            B=B, n_tiles=len(tiles), cu=torch.tensor(cu, dtype=torch.int32, device=dev),
+            tiles=torch.tensor(tiles, dtype=torch.int32, device=dev).reshape(-1, 2).contiguous())
+        st = _hip.stream()
+        _hip.call("llj_embedding", ids.data_ptr(), self.transformer.wte.weight.data_ptr(), w.x.data_ptr(), M,
+                  cfg.n_embd, None, st)
+        self._blocks_gemm(w, specs, kv, None, 1, M, S, st)
+        last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64, device=dev)
+        self._head(w.x.index_select(0, last), B, specs, last_only_out, st, w)
+        return last_only_out
+
     def ragged_support(self) -> Optional[str]:
         """None if this model decodes rows at a position each (DecodeSession.prefill_ragged,
         generate.generate_prompts), else why not. The route takes streaming-path models whose Linears are
@@ -767,11 +832,20 @@ class LLaMA(nn.Module):
                     _hip.call("llj_gemm_qkv_rope_lora", _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa),
                               w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(),
                               B, T, C, nh, S, st, *_lora_tail(lo, w.lt))
+                elif w.packed is not None:  # packed sequences: c_attn's plain store, then RoPE + KV write by cu
+                    pk, rope = w.packed, self.rope_cache
+                    _lcall("llj_gemm_linear", aa, _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), C, wa.data_ptr(), P(sa),
+                           w.qkv.data_ptr(), 3 * C, M, 3 * C, C, st)
+                    _hip.call("llj_rope_kv_packed", w.qkv.data_ptr(), w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                              rope.data_ptr(), pk.cu.data_ptr(), pk.B, M, nh, C // nh, S, rope.shape[0], st)
                 else:
                     _lcall("llj_gemm_qkv_rope", aa, _gz(fa, blk.attn.c_attn), w.xn.data_ptr(), wa.data_ptr(), P(sa),
                            w.q.data_ptr(), kc.data_ptr(), vc.data_ptr(), self.rope_cache.data_ptr(), pos.data_ptr(), B,
                            T, C, nh, S, st)
-            self._attention(w, kc, vc, pos, B, T, S, st, i)
+            if w.packed is not None:
+                self._attention_packed(w, kc, vc, M, S, st, i)
+            else:
+                self._attention(w, kc, vc, pos, B, T, S, st, i)
             self._gemm_resid(_gz(fp, blk.attn.c_proj), w.y, wp, sp, w.x, M, C, C, w, st, ap)
             if f1 != f2:
                 raise TypeError("c_fc1 and c_fc2 must share a weight format")
